@@ -47,6 +47,12 @@ The line also carries `roofline` (live HIP-event timing of the kernel vs the
 8 TB/s HBM peak, PMC traffic) and, at N=1, `cpu_baseline` (the oracle's
 auto-vectorised C restatement of the reference's scalar loop, timed on this
 box's host cores on a bounded sample).
+
+--dump-outputs DIR writes what each leg's last timed step computed, for comparing two builds output for
+output: a fixed, seeded sample of whole blocks of the decoded (or packed) column as float64 .npy files,
+exact (values of up to 32 bits as they are, u64 as its low and high 32-bit halves), next to the sampled
+global block indices.  The inputs are counter-based streams of fixed seeds, so the same arguments give
+the same inputs on every run.
 """
 import argparse
 import json
@@ -61,6 +67,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_COPY_CEILING_GBPS = 6290.0  # same table: measured float4-copy ceiling
 CONFIG5_BLOCKS = 9_765_625      # 10 B integers / 1024 (BASELINE.json configs[4])
+DUMP_BLOCKS = 2048              # --dump-outputs: blocks per leg; at most 16 KiB of float64 per block (u64 unpack) -> 48 MiB for both legs
 
 WORKLOADS = {
     # name: (type, width, op, bytes per block = SURVEY.md 8(d): 128*W + 128*T [+128 bases])
@@ -135,7 +142,16 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher plumbing only, no GPU: spawn / rendezvous / barrier / max-reduce / sharding run for "
                          "real, the codec step is skipped and the line says so (value null) -- never a measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after each leg's timed steps, write a seeded sample of whole blocks of what its last step computed to "
+                         "DIR/<leg>_output.npy (float64; u64: _output_lo / _output_hi, the 32-bit halves) and the sampled global "
+                         f"block indices to DIR/<leg>_blocks.npy; {DUMP_BLOCKS} blocks per leg over all ranks, under 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the codec step: not with --dry-run")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -654,6 +670,30 @@ def timed_region(step, args, ctl):
     return ctl.all_max(elapsed), kern_ms
 
 
+def dump_outputs(w, leg, first_block, args, world, rank):
+    """--dump-outputs: whole blocks of what the last timed step wrote (w.dst, n equal blocks), sampled with a fixed seed -- the first and
+    last block of this rank's slice among them -- as float64 .npy files.  Call it before anything else writes w.dst."""
+    import numpy as np
+    import torch
+    n = w.n
+    k = min(n, max(2, DUMP_BLOCKS // world))
+    idx = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(0).choice(n, k - 2, replace=False)])) if k < n else np.arange(n)
+    rows = w.dst.view(torch.uint8).view(n, -1)
+    npdt = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "u64": np.uint64}[w.ty]
+    vals = rows.index_select(0, torch.from_numpy(idx).to(rows.device)).cpu().numpy().view(npdt)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(args.dump_outputs, f"{leg}_{name}{sfx}.npy"), a.astype(np.float64))
+    save("blocks", idx + first_block)
+    if w.ty == "u64":                # float64 holds 53 bits: the two halves keep every bit
+        save("output_lo", vals & np.uint64(0xFFFFFFFF))
+        save("output_hi", vals >> np.uint64(32))
+    else:
+        save("output", vals)
+
+
 # ---------------------------------------------------------------------------------------------
 # PMC traffic (N=1): the workload's kernel re-run under rocprofv3, separate passes per counter
 # ---------------------------------------------------------------------------------------------
@@ -900,6 +940,8 @@ def config5_leg(args, world, rank, dev, ctl):
                                                "blocks": int(v[0])} for r, v in enumerate(per_rank)]}
     w, probe = placed_workload("u32_mixed_unpack", n, first, rank, dev, args, args.single_device)
     elapsed, kern_ms = timed_region(w.step, args, ctl)
+    if args.dump_outputs:
+        dump_outputs(w, "config5_strong", first, args, world, rank)
     avg_ms = sum(kern_ms) / len(kern_ms)
     per_rank = ctl.gather([float(n), avg_ms, float(w.bytes)])
     flags, n_checked, verified = run_check(w, args, ctl)
@@ -1006,6 +1048,8 @@ def main():
 
     w, probe = placed_workload(args.workload, n, first, rank, dev, args, args.single_device)
     elapsed, kern_ms = timed_region(w.step, args, ctl)
+    if args.dump_outputs:
+        dump_outputs(w, args.workload, first, args, world, rank)
     avg_ms = sum(kern_ms) / len(kern_ms)
     per_rank = ctl.gather([float(n), avg_ms, float(w.bytes)])
     flags, n_checked, verified = run_check(w, args, ctl)       # every rank, its own slice, outside the timed region

@@ -89,3 +89,12 @@ def test_one_mismatching_rank_fails_every_rank():
     out = _one_json_line(r.stdout)
     assert [p["correct"] for p in out["per_rank"]] == [True, False]
     assert "MISMATCH" in out["correctness"] and "1" in out["correctness"]
+
+
+@pytest.mark.parametrize("extra", [["--steps", "0"], ["--warmup", "-1"], ["--dry-run", "--dump-outputs", "dumps"]])
+def test_arguments_that_cannot_run_are_refused(extra, tmp_path):
+    """--steps is the number of timed steps (at least one: the line divides by it); --dump-outputs needs the codec step."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + extra, capture_output=True, text=True, timeout=300, env=_clean_env(),
+                       cwd=tmp_path)
+    assert r.returncode == 2 and "error:" in r.stderr, r.stderr
+    assert not os.listdir(tmp_path)

@@ -1750,6 +1750,44 @@ def test_bench_two_ranks_on_this_gpu(fl, backend):
             assert d["control_fallback_reason"]
 
 
+def test_bench_dump_outputs(fl, oracle, tmp_path):
+    """bench.py --dump-outputs DIR: a seeded sample of whole blocks of what each leg's last timed step wrote, float64, under 64 MB in
+    all, every sampled block equal to the oracle decoding the same counter-based input stream (fl_fill_random, seed 1234 on rank 0)
+    regenerated on the host."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    n, W = 300_000, 7
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", str(n),
+                        "--placement", "separate", "--verify", "sample", "--no-cpu-baseline", "--no-pmc", "--no-dispatch-check",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["config5_strong_blocks.npy", "config5_strong_output.npy", "u32_w7_unpack_blocks.npy", "u32_w7_unpack_output.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    GOLDEN, M64 = 0x9E3779B97F4A7C15, (1 << 64) - 1
+
+    def regenerated(first_word, n_words):
+        return oracle.parallel_fill(np.empty(n_words, dtype=np.uint64), 8, n_words, (1234 * GOLDEN + first_word * GOLDEN) & M64, 8)
+    # u32 W=7 (n blocks): block b is 16 * W 64-bit words from word b * 16 * W
+    blocks = np.load(tmp_path / "u32_w7_unpack_blocks.npy")
+    out = np.load(tmp_path / "u32_w7_unpack_output.npy")
+    assert blocks.dtype == out.dtype == np.float64 and out.shape == (len(blocks), 1024) and len(blocks) > 1000
+    blocks = blocks.astype(np.int64)
+    assert blocks[0] == 0 and blocks[-1] == n - 1 and (np.diff(blocks) > 0).all()
+    for b, row in zip(blocks.tolist(), out):
+        assert np.array_equal(row, oracle.unpack("u32", W, regenerated(b * 16 * W, 16 * W).view(np.uint32)).astype(np.float64)), b
+    # the strong-scaled mixed-width column: width[b] = 1 + b mod 32, block b at byte offset sum of 128 * width over the blocks before it
+    blocks = np.load(tmp_path / "config5_strong_blocks.npy").astype(np.int64)
+    out = np.load(tmp_path / "config5_strong_output.npy")
+    assert out.shape == (len(blocks), 1024) and blocks[0] == 0 and blocks[-1] == 9_765_625 - 1
+    for b, row in zip(blocks.tolist(), out):
+        w = 1 + b % 32
+        first_word = 16 * (528 * (b // 32) + (b % 32) * (b % 32 + 1) // 2)
+        assert np.array_equal(row, oracle.unpack("u32", w, regenerated(first_word, 16 * w).view(np.uint32)).astype(np.float64)), b
+
+
 # ---------------------------------------------------------------------------
 # Under load.  The per-(T, W) tests above run tens of blocks: a handful of wavefronts on an idle chip.  A kernel can be right
 # there and wrong with every CU busy (round 3: a register-only form of Delta's lane-group scan passed all of them and produced
@@ -1859,7 +1897,13 @@ def test_column_pair_alloc_and_the_bare_stream(fl, oracle):
             assert pair.output.data_ptr() - pair.input.data_ptr() == ((64 << 30) - half) // 256 * 256
         if layout == "auto":
             assert pair.probe_GBps and set(pair.probe_GBps) <= {"separate", "zoned"} and all(v > 50 for v in pair.probe_GBps.values())
-            assert pair.layout == max(pair.probe_GBps, key=pair.probe_GBps.get)
+            # the header's rule: SEPARATE is timed first and ZONED replaces it only if it is more than 2 % faster (a pair this
+            # small has no INTERLEAVED candidate); the figures are rounded to whole GB/s, so a tie within 1 GB/s of the threshold says nothing
+            p = pair.probe_GBps
+            if "zoned" not in p:
+                assert pair.layout == "separate", p
+            elif abs(p["zoned"] - 1.02 * p["separate"]) > 1:
+                assert pair.layout == ("zoned" if p["zoned"] > 1.02 * p["separate"] else "separate"), p
         else:
             assert pair.probe_GBps is None
         pair.input.view(torch.uint32).copy_(to_dev(pk))
