@@ -78,7 +78,7 @@ def _signatures(ty):
 INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_policy", "fl_internal_probe_memory_classes",
                     "fl_internal_bare_stream", "fl_internal_bare_stream_shape", "fl_internal_zero_copy_fallbacks",
                     "fl_internal_column_pair_classes", "fl_internal_selftune_check", "fl_internal_choose_chunks",
-                    "fl_internal_pair_chunk_cache"]
+                    "fl_internal_choose_layout", "fl_internal_pair_chunk_cache"]
 
 
 def exported_symbols():
@@ -160,6 +160,8 @@ def load():
     lib.fl_internal_pair_chunk_cache.argtypes = [_Z]
     lib.fl_internal_choose_chunks.restype = ctypes.c_size_t
     lib.fl_internal_choose_chunks.argtypes = [ctypes.POINTER(ctypes.c_int), _Z, _Z, _Z, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.fl_internal_choose_layout.restype = ctypes.c_int
+    lib.fl_internal_choose_layout.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.fl_internal_column_pair_classes.restype = ctypes.c_char_p
     lib.fl_internal_column_pair_classes.argtypes = [_P]
     lib.fl_widths_to_offsets.restype = ctypes.c_int

@@ -80,13 +80,13 @@ inline std::atomic<int>& window_override()
     static std::atomic<int> v{0};
     return v;
 }
-// the same for the calling thread's launches only (the memory-class probe of fl_capi.hip); wins over the process-wide one
+// the same for the calling thread's launches only (the memory-class probe of fl_pair.hip); wins over the process-wide one
 inline int& window_override_this_thread()
 {
     static thread_local int v = 0;
     return v;
 }
-// set by every device-tier entry point of the C ABI (fl_capi.hip: FL_DEVICE_TIER) for the launches it makes: the call's buffers lie
+// set by every device-tier entry point of the C ABI (fl_host.hpp: FL_DEVICE_TIER) for the launches it makes: the call's buffers lie
 // inside one live FL_LAYOUT_INTERLEAVED pair.  Such a pair has its input inside one class of memory and its output rotating through
 // classes by the whole-column map's write positions; the table's windows are for plain allocations (they keep the eight XCDs' reads
 // inside one class) and lose 1-4 % here on every row that has one (profiles/r06_window_matrix_constructed.txt).

@@ -51,13 +51,20 @@
  * HIP calls: an application that relies on hipGetLastError across a call into this
  * library must read it before the call.
  *
- * Threading and device selection.  Re-entrant and thread-safe; no global state
- * besides HIP's own, and no entry point ever calls hipSetDevice.  The device is
- * selected the way HIP selects it: kernels run on the device that is CURRENT for
- * the calling thread, so `stream` (when not NULL) must be a stream of that device
- * and every device pointer must be memory that device can use (its own HBM,
- * managed memory, or pinned host memory).  One host thread per device, each after
- * its own hipSetDevice, is the intended multi-GPU shape (examples/multi_gpu_decode.c).
+ * Threading and device selection.  Re-entrant and thread-safe.  The library's own
+ * state: per host thread, the host tier's context (stream and staging buffers,
+ * fl_host_release); per device, the grid sizes of the persistent kernels; per
+ * process, the kernel-policy and tile-map overrides of fastlanes_amd_internal.h,
+ * and for fl_column_pair_alloc the registry of live FL_LAYOUT_INTERLEAVED pairs,
+ * the address ranges such pairs have used and a chunk cache (empty unless a tool
+ * enables it).  No entry point changes the calling thread's current device
+ * (fl_column_pair_free switches to the pair's device for a moment and switches
+ * back).  The device is selected the way HIP selects it: kernels run on the
+ * device that is CURRENT for the calling thread, so `stream` (when not NULL)
+ * must be a stream of that device and every device pointer must be memory that
+ * device can use (its own HBM, managed memory, or pinned host memory).  One host
+ * thread per device, each after its own hipSetDevice, is the intended multi-GPU
+ * shape (examples/multi_gpu_decode.c).
  * A mismatch -- device 0 current, buffers or stream of device 1 -- is undefined
  * behaviour by default, exactly as for a raw kernel launch; with the environment
  * variable FL_CHECK_DEVICE=1 (read once, at the first device-tier call) every
@@ -153,8 +160,9 @@ int fl_fill_random(void *dst, size_t n_bytes, uint64_t seed, void *stream);
  *                          candidate; `stream` must not be capturing), and the buffers' contents are unspecified afterwards.  A candidate
  *                          that cannot be allocated is skipped; pairs too small to time (< 4 MiB) are allocated SEPARATE.
  * in / aux / out receive in_bytes / aux_bytes / out_bytes bytes (256-byte aligned; aux_bytes may be 0: *aux = NULL, aux itself may then
- * be NULL); *handle owns the memory: fl_column_pair_free(handle) releases it (NULL is a no-op).  layout_kept (may be NULL) receives
- * the layout of the returned pair, probe_gbps (may be NULL; FL_LAYOUT_COUNT entries, indexed by layout, the FL_LAYOUT_PROBE slot stays
+ * be NULL); *handle owns the memory: fl_column_pair_free(handle) releases it (NULL is a no-op) after waiting for the work queued on its
+ * device, whatever the layout (hipFree waits the same way), so it may follow launches on the pair's buffers at once.  layout_kept (may
+ * be NULL) receives the layout of the returned pair, probe_gbps (may be NULL; FL_LAYOUT_COUNT entries, indexed by layout, the FL_LAYOUT_PROBE slot stays
  * 0) the probe's GB/s (0 = not measured).  This is what bench.py's --placement auto does: the figure it prints is one this header
  * alone reproduces.
  * (An INTERLEAVED pair's addresses are never handed out twice within a process: on this ROCm (7.2) an address range that is unmapped and

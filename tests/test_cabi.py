@@ -33,14 +33,15 @@ def _header_symbols():
 def test_every_declared_symbol_is_exported(lib):
     import fastlanes_amd
     syms = _header_symbols()
-    assert len(syms) == 4 * 42 + 25
+    assert len(syms) == 4 * 42 + 26
     assert sorted(fastlanes_amd.exported_symbols()) == syms
     for s in syms:
         assert hasattr(lib, s), s
 
 
 def test_column_pair_and_bare_stream_argument_checks_need_no_gpu(lib):
-    """fl_column_pair_alloc / fl_internal_bare_stream(_shape): every refusal happens before the first HIP call"""
+    """fl_column_pair_alloc / fl_internal_bare_stream(_shape): every refusal happens before the first HIP call; the layout FL_LAYOUT_PROBE
+    keeps is decided by a pure host function"""
     P = ctypes.c_void_p
     i, a, o, h = P(), P(), P(), P()
     kept = ctypes.c_int(-1)
@@ -49,6 +50,26 @@ def test_column_pair_and_bare_stream_argument_checks_need_no_gpu(lib):
     assert lib.fl_column_pair_alloc(1 << 20, 0, 1 << 20, 4, None, ctypes.byref(i), None, ctypes.byref(o), ctypes.byref(h), ctypes.byref(kept), None) == 2   # FL_LAYOUT_COUNT
     assert lib.fl_column_pair_alloc(1 << 20, 0, 1 << 20, -1, None, ctypes.byref(i), None, ctypes.byref(o), ctypes.byref(h), ctypes.byref(kept), None) == 2
     assert lib.fl_column_pair_free(None) == 0
+    # fl_internal_choose_layout = FL_LAYOUT_PROBE's keep / replace rule (a pure host function): the candidates in the order INTERLEAVED,
+    # SEPARATE, ZONED; the first allocated one is kept; a later one replaces it only if faster by more than 1 %, ZONED by more than 2 %
+    SEP, ZON, ITL = 0, 1, 3                                  # FL_LAYOUT_SEPARATE, _ZONED, _INTERLEAVED
+    NA = -1.0
+
+    def choose(separate, zoned, interleaved):
+        g = [NA] * 4
+        g[SEP], g[ZON], g[ITL] = separate, zoned, interleaved
+        return lib.fl_internal_choose_layout((ctypes.c_double * 4)(*g))
+    assert choose(100.0, 101.0, NA) == SEP                   # ZONED needs more than 2 %
+    assert choose(100.0, 103.0, NA) == ZON
+    assert choose(100.9, NA, 100.0) == ITL                   # any other later candidate more than 1 %
+    assert choose(101.5, NA, 100.0) == SEP
+    assert choose(101.5, 103.0, 100.0) == SEP and choose(101.5, 103.6, 100.0) == ZON
+    assert choose(100.0, 100.0, NA) == SEP                   # interleaved not allocated: SEPARATE is the first candidate
+    assert choose(NA, 100.0, NA) == ZON
+    assert choose(0.0, 0.0, 0.0) == ITL                      # all zeros (nothing measured): the first allocated candidate
+    assert choose(0.0, 0.0, NA) == SEP
+    assert choose(NA, NA, NA) == -1 and lib.fl_internal_choose_layout(None) == -1
+    assert lib.fl_internal_choose_layout((ctypes.c_double * 4)(NA, NA, 500.0, NA)) == -1     # the FL_LAYOUT_PROBE slot is not a candidate
     Z, I = ctypes.c_size_t, ctypes.c_int
     iu, au, ou, nt, wv, wn, bpu = Z(), Z(), Z(), I(), I(), I(), ctypes.c_uint()
     refs = [ctypes.byref(x) for x in (iu, au, ou, nt, wv, wn, bpu)]
@@ -311,11 +332,13 @@ def test_zone_aware_placement_helper_arithmetic():
 
 def test_constructed_layout_chooses_chunks_by_class(lib):
     """fl_internal_choose_chunks = the arrangement FL_LAYOUT_INTERLEAVED makes from a measured class map (a pure host function): the input
-    inside ONE class; the output rotating through the other two classes (a write-dominated pair) or through all three, by POSITION -- the
-    k-th chunk of the x-th eighth takes letter (x + k), so that the eight XCDs' write positions under the whole-column tile map cycle
-    through the classes at every moment; a scarce class's positions go to the largest surplus, classes outside the rotation first; no
-    chunk used twice; creation order where no class can hold the input (unpack u32 W=7 in A | out B/C 0.865, out
-    A/B/C 0.860, out A/B 0.855, out B alone 0.80, out A 0.78 of the peak; pack u32 W=7 out A/B/C 0.859, out B/C 0.84)."""
+    inside ONE class; the output labelled from the other two classes (a write-dominated pair) or from all three by a SEARCH -- the cost is
+    the mean over 64 values of the progress t of the cubed class counts under the eight XCDs' write positions (whole-column tile map), plus
+    a fee for chunks from outside the rotation (600 for the input's own class, halved where the rotation's classes are scarce,
+    FL_INTERNAL_OWN_CLASS_FEE overrides it) and a penalty per chunk a class does not have -- so the eight positions are spread over the
+    classes at every moment; no chunk used twice; creation order where no class can hold the input (unpack u32 W=7
+    in A | out B/C 0.865, out A/B/C 0.860, out A/B 0.855, out B alone 0.80, out A 0.78 of the peak; pack u32 W=7 out A/B/C 0.859, out
+    B/C 0.84)."""
     import random
 
     def choose(classes, n_in, n_out, out_classes=2):

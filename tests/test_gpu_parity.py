@@ -1941,8 +1941,9 @@ def test_column_pair_alloc_and_the_bare_stream(fl, oracle):
 def test_interleaved_column_pair_is_constructed_from_measured_chunks(fl, oracle, n_blocks):
     """FL_LAYOUT_INTERLEAVED (round 6): the pair is built from 1-GiB physical chunks whose class of memory
     was measured; input + aux inside one class, the output's chunks arranged for the eight XCDs' write positions.  The codec decodes in it exactly as in
-    plain allocations (oracle on the blocks around every chunk boundary, the whole output against a plain-allocation decode), a second
-    pair never gets the first one's addresses (this ROCm keeps stale translations for re-used ranges: tools/exp_vmm remap), and
+    plain allocations (oracle on the blocks around every chunk boundary, the whole output against a plain-allocation decode), freeing it
+    waits for the work queued on the device, a second pair never gets the first one's addresses (this ROCm keeps stale translations for
+    re-used ranges: tools/exp_vmm remap), and
     "auto" reports the constructed layout's figure next to the others."""
     import torch
     from fastlanes_amd import placement as pl
@@ -1976,7 +1977,20 @@ def test_interleaved_column_pair_is_constructed_from_measured_chunks(fl, oracle,
         want = oracle.batch("unpack", "u32", W, np.ascontiguousarray(host_pk[edges]).reshape(-1)).reshape(len(edges), 1024)
         assert np.array_equal(host_out[edges], want)
         pairs.append((pair.input.data_ptr(), pair.output.data_ptr() + ob))
+        # fl_column_pair_free waits for queued work as hipFree does, whatever the layout: ~100 ms of decodes between plain tensors
+        # (nothing queued touches the pair) on a non-blocking side stream are complete when it returns
+        side, spare = torch.cuda.Stream(), torch.empty_like(plain)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(70):
+                fl.BitPacking.unpack(W, pk, output=spare)
+        queued = torch.cuda.Event()
+        queued.record(side)
         pair.free()
+        drained = queued.query()
+        torch.cuda.synchronize()
+        del spare
+        assert drained, "fl_column_pair_free returned before the work queued on the device had finished"
     (a0, a1), (b0, b1) = pairs
     assert b0 >= a1 or b1 <= a0, "an interleaved pair re-used a freed pair's addresses"
     # the encode direction: a read-dominated pair's output rotates through ALL three classes, and calls whose buffers lie inside one live

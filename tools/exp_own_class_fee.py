@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How much of a write-dominated pair's output may come from the INPUT's class of memory?  fl_column_pair_alloc's arrangement search charges a fee
-per chunk of the output taken from outside the rotation (fl_capi.hip: choose_chunks; 300 is about break-even with the balance one such chunk buys, 600 is shipped);
+per chunk of the output taken from outside the rotation (fl_pair.hip: choose_chunks; 300 is about break-even with the balance one such chunk buys, 600 is shipped);
 FL_INTERNAL_OWN_CLASS_FEE sets it.  One process per fee (the fee is read once), same box, headline shape; prints the class map and the rate.
     for f in 300 1000 150; do FL_INTERNAL_OWN_CLASS_FEE=$f python tools/exp_own_class_fee.py; done"""
 import os, statistics, sys
