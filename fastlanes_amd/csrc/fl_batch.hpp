@@ -21,8 +21,8 @@ struct BatchArgs {
     uint32_t* err_flag;          // FL_DEVERR_* bits; may be nullptr
     const void* refs;            // FoR: references[a], one per ARRAY (ffor.rs:24-50); nullptr = plain BitPacking
     uint64_t n_arrays;
-    uint64_t tiles_per_xcd;
-    unsigned window_shift;       // tile-map window (fl_kernels.hpp: xcd_tile)
+    uint64_t tiles_per_xcd = 0;
+    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile)
     unsigned tiles_per_array;    // ceil(max_blocks / (4 * bpw))
     unsigned max_blocks;         // the caller's bound on n_blocks[a]
     unsigned bpw;                // consecutive blocks of the array per wavefront (>= 1); a workgroup takes 4 * bpw
@@ -173,14 +173,9 @@ hipError_t launch_batch_chain(const BatchArgs& b0, uint32_t max_blocks, int wave
     b.prefetch = 0;
     b.tiles_per_array = (unsigned)(((uint64_t)max_blocks + TILE_BLOCKS - 1) / TILE_BLOCKS);
     b.max_blocks = max_blocks;
-    const uint64_t n_tiles = b.n_arrays * b.tiles_per_array;
-    b.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (b.tiles_per_array == 0 || b.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;
-    b.window_shift = tile_window_shift(chain_window_op<SRC, BODY, SNK>(), WaveBlock<T>::TB, TILE_BLOCKS);
-    const unsigned need = TILE_BLOCKS * chain_wave_lds<T, SRC, SNK>();
-    if (waves < 3) waves = 3;
-    const unsigned pad = (CU_LDS_BYTES * (unsigned)WG / ((unsigned)waves * 256u)) & ~1023u;
-    FL_LAUNCH((k_batch_chain<T, SRC, BODY, SNK>), dim3((unsigned)(b.tiles_per_xcd * 8)), dim3(WG), pad > need ? pad : need, s, b);
+    const unsigned grid = plan_tiles(b, b.n_arrays * b.tiles_per_array, tile_window_shift(chain_window_op<SRC, BODY, SNK>(), WaveBlock<T>::TB, TILE_BLOCKS));
+    if (!grid) return hipErrorInvalidValue;
+    FL_LAUNCH((k_batch_chain<T, SRC, BODY, SNK>), dim3(grid), dim3(WG), occupancy_lds(waves, TILE_BLOCKS * chain_wave_lds<T, SRC, SNK>()), s, b);
     return hipGetLastError();
 }
 
@@ -193,19 +188,14 @@ hipError_t launch_batch(const BatchArgs& b0, uint32_t max_blocks, int waves, hip
 {
     if (b0.n_arrays == 0 || max_blocks == 0) return hipSuccess;
     BatchArgs b = b0;
-    if (b.bpw == 0) b.bpw = 1;
-    if (b.bpw < 2 || b.bpw > 16) b.prefetch = 0;
-    if (b.prefetch && (WG / 64) * b.bpw * WaveBlock<T>::BLOCK_BYTES > 64u * 1024u) b.prefetch = 0;   // images would not fit a workgroup's LDS
+    const unsigned need = tidy_wave_blocks<T>(b.bpw, b.prefetch);
     const uint64_t tile_blocks = (uint64_t)b.bpw * (WG / 64);
     b.tiles_per_array = (unsigned)(((uint64_t)max_blocks + tile_blocks - 1) / tile_blocks);            // 64-bit: no wrap near 2^32
     b.max_blocks = max_blocks;
-    const uint64_t n_tiles = b.n_arrays * b.tiles_per_array;
-    b.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (b.tiles_per_array == 0 || b.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;
-    b.window_shift = tile_window_shift(PACK ? WIN_PACK : WIN_UNPACK, WaveBlock<T>::TB, (unsigned)tile_blocks);
-    const unsigned lds = widths_lds_bytes<T>(waves, b.prefetch ? b.bpw : 1u);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    FL_LAUNCH((k_batch<T, PACK>), dim3((unsigned)(b.tiles_per_xcd * 8)), dim3(WG), lds, s, b);
+    const unsigned grid = plan_tiles(b, b.n_arrays * b.tiles_per_array, tile_window_shift(PACK ? WIN_PACK : WIN_UNPACK, WaveBlock<T>::TB, (unsigned)tile_blocks));
+    const unsigned lds = occupancy_lds(waves, need);
+    if (!grid || lds > 64 * 1024) return hipErrorInvalidValue;
+    FL_LAUNCH((k_batch<T, PACK>), dim3(grid), dim3(WG), lds, s, b);
     return hipGetLastError();
 }
 

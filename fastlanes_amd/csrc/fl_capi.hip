@@ -25,22 +25,52 @@ namespace {
 
 using namespace fl;
 
-// fl_internal_set_kernel_policy: 0 = the generated table (fl_dispatch.hpp), 1 = cell-column kernels wherever they are
-// built, 2 = wave-per-block kernels wherever they exist.  Results are bit-identical; only speed differs.
+// fl_internal_set_kernel_policy (validated there).  mode 0 = the generated table (fl_dispatch.hpp), 1 = cell-column kernels wherever
+// they are built, 2 = wave-per-block kernels wherever they exist.  Under mode 2 the A/B tools may also force waves per SIMD (policy
+// 2 + 256 * waves) and blocks per wavefront (+ 65536 * bpw, + 2^24: prefetch); bits 25-29 are the tile-map window (window_override).
+// Results are bit-identical; only speed differs.
 std::atomic<int> g_kernel_policy{0};
-
-// waves per SIMD to run the wave-per-block kernel at, or 0 = use the cell-column kernel.  The per-(T,W) cell-column
-// families are only built where the table chose them (cell_column_built); Delta's / Transpose's per-type cell-column
-// kernels (no width parameter) always exist.
-inline int chosen_waves(unsigned type_bits, unsigned w, fl::WaveOp op)
+struct KernelPolicy {
+    int mode;
+    int waves;            // 0 = the launch's own
+    unsigned bpw;         // 0 = the launch's own blocks per wavefront and prefetch
+    unsigned prefetch;
+};
+inline KernelPolicy kernel_policy()
 {
     const int p = g_kernel_policy.load(std::memory_order_relaxed);
-    const int table = fl::wave_policy(type_bits, w, op);
+    const bool ab = (p & 0xff) == 2;
+    return {p & 0xff, ab ? (p >> 8) & 0xff : 0, ab ? (unsigned)(p >> 16) & 0xffu : 0u, (unsigned)(p >> 24) & 1u};
+}
+
+// The shape of a wave-per-block launch: waves per SIMD, blocks per wavefront, prefetch (fl_widths.hpp).  Each family's default comes
+// from fl_dispatch.hpp; with_policy lays the A/B tools' overrides over it (the launcher tidies bpw / prefetch: tidy_wave_blocks).
+struct WaveShape {
+    int waves;
+    unsigned bpw = 1, prefetch = 0;
+};
+inline WaveShape with_policy(WaveShape sh)
+{
+    const KernelPolicy p = kernel_policy();
+    if (p.waves) sh.waves = p.waves;
+    if (p.bpw) { sh.bpw = p.bpw; sh.prefetch = p.prefetch; }
+    return sh;
+}
+
+// The kernel the policy gives a uniform-width (T, W, op): waves per SIMD for the wave-per-block kernel (0 = the cell-column kernel), and
+// whether it takes two blocks per wavefront (fl_dispatch.hpp: wave_choice).  The per-(T,W) cell-column families are only built where
+// the table chose them (cell_column_built); Delta's / Transpose's per-type cell-column kernels (no width parameter) always exist.
+inline WaveChoice chosen_waves(unsigned type_bits, unsigned w, fl::WaveOp op)
+{
+    const KernelPolicy p = kernel_policy();
+    const WaveChoice table = fl::wave_choice(type_bits, w, op);
     const bool per_type = op == fl::WAVE_UNDELTA || op == fl::WAVE_DELTA || op == fl::WAVE_TRANSPOSE || op == fl::WAVE_UNTRANSPOSE;
-    if ((p & 0xff) == 1) return (per_type || fl::cell_column_built(type_bits, w, op)) ? 0 : table;
-    if ((p & 0xff) != 2) return table;
-    if ((p >> 8) & 0xff) return (p >> 8) & 0xff;     // A/B tools: policy 2 + 256 * waves forces the occupancy too
-    return table ? table : fl::wave_fallback(type_bits, op == fl::WAVE_PACK || op == fl::WAVE_FOR_PACK || op == fl::WAVE_TRANSPOSE_DELTA_PACK);
+    if (p.mode == 1) return (per_type || fl::cell_column_built(type_bits, w, op)) ? WaveChoice{0, false} : table;
+    if (p.mode != 2) return table;
+    const bool pack = op == fl::WAVE_PACK || op == fl::WAVE_FOR_PACK || op == fl::WAVE_TRANSPOSE_DELTA_PACK;
+    WaveChoice c = p.waves ? WaveChoice{p.waves, false} : table.waves ? table : WaveChoice{fl::wave_fallback(type_bits, pack), false};
+    if (p.bpw) c.two_blocks = p.bpw == 2;         // the A/B tools force either form: 2 + 256 * waves + 65536 * {1, 2}
+    return c;
 }
 
 template <typename T>
@@ -59,8 +89,6 @@ int run_stream(stream_launch_t fn, const T* in, T* out, const void* aux, size_t 
     a.aux = aux;
     a.aux_stride = aux_stride;
     a.n_blocks = n_blocks;
-    a.tiles_per_xcd = 0;   // filled by the launcher
-    a.window_shift = 63;   // filled by the launcher
     return hip_status(fn(a, static_cast<hipStream_t>(stream)));
 }
 
@@ -96,8 +124,6 @@ int run_chain(int op, int waves, unsigned w, const T* in, const T* bases, T* out
     a.out = reinterpret_cast<char*>(out);
     a.bases = reinterpret_cast<const char*>(bases);
     a.n_blocks = n_blocks;
-    a.tiles_per_xcd = 0;
-    a.window_shift = 63;
     a.width = w;
     a.widths = widths;
     a.offsets = offsets;
@@ -124,24 +150,21 @@ int run_wave_uniform(bool pack, int waves, unsigned w, const T* packed, T* unpac
     a.refs = refs;
     a.ref_stride = ref_stride;
     a.n_blocks = n_blocks;
-    a.tiles_per_xcd = 0;
-    a.window_shift = 63;
     a.uniform_width = w;
-    a.bpw = uniform_blocks_per_wave(Elem<T>::BITS, pack, w, refs != nullptr);
+    const unsigned bpw = uniform_blocks_per_wave(Elem<T>::BITS, pack, w, refs != nullptr);
+    const WaveShape sh = with_policy({waves, bpw, bpw > 1});
+    a.bpw = sh.bpw;
     a.packed_bytes = 0;      // not read: uniform-width calls are validated here, on the host side
-    a.prefetch = a.bpw > 1;
+    a.prefetch = sh.prefetch;
     a.linear_map = 0;
     a.nt_from = fl::nt_read_from(Elem<T>::BITS);
-    const int pol = g_kernel_policy.load(std::memory_order_relaxed);       // A/B tools: 2 + ... + 65536 * blocks-per-wavefront (+ 2^24: prefetch)
-    if ((pol & 0xff) == 2 && ((pol >> 16) & 0xff)) { a.bpw = (pol >> 16) & 0xff; a.prefetch = (pol >> 24) & 1; }
-    if (a.prefetch && (WG / 64) * a.bpw * WaveBlock<T>::BLOCK_BYTES > 64u * 1024u) a.prefetch = 0;   // images would not fit a workgroup's LDS
-    return hip_status(widths_launcher<T>(pack)(a, waves, static_cast<hipStream_t>(stream)));
+    return hip_status(widths_launcher<T>(pack)(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 template <typename T> int dev_pack(unsigned w, const T* in, T* out, size_t n, void* s)
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_PACK)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_PACK).waves) {
         if (n && !in) return FL_ERR_NULL;
         return run_wave_uniform<T>(true, waves, w, out, const_cast<T*>(in), nullptr, 0, n, s);
     }
@@ -150,7 +173,7 @@ template <typename T> int dev_pack(unsigned w, const T* in, T* out, size_t n, vo
 template <typename T> int dev_unpack(unsigned w, const T* in, T* out, size_t n, void* s)
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNPACK))
+    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNPACK).waves)
         return run_wave_uniform<T>(false, waves, w, in, out, nullptr, 0, n, s);
     return run_stream<T>(unpack_table_impl<T, BODY_STORE>().fn[w], in, out, nullptr, 0, n, w != 0, true, false, s);
 }
@@ -158,7 +181,7 @@ template <typename T>
 int dev_for_pack(unsigned w, const T* in, const T* refs, size_t stride, T* out, size_t n, void* s)
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_FOR_PACK)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_FOR_PACK).waves) {
         if (n && (!in || !refs)) return FL_ERR_NULL;
         return run_wave_uniform<T>(true, waves, w, out, const_cast<T*>(in), refs, stride, n, s);
     }
@@ -168,7 +191,7 @@ template <typename T>
 int dev_unfor_pack(unsigned w, const T* in, const T* refs, size_t stride, T* out, size_t n, void* s)
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNFOR_PACK)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNFOR_PACK).waves) {
         if (n && !refs) return FL_ERR_NULL;
         return run_wave_uniform<T>(false, waves, w, in, out, refs, stride, n, s);
     }
@@ -179,14 +202,8 @@ int dev_undelta_pack(unsigned w, const T* in, const T* bases, T* out, size_t n, 
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNDELTA_PACK)) {
-        // a table entry 10 + k = the wave-per-block kernel with TWO blocks per wavefront in lockstep at k waves per SIMD (fl_dispatch.hpp);
-        // the A/B tools force either form with the policy's blocks-per-wavefront field (2 + 256 * waves + 65536 * {1, 2})
-        bool two = waves >= TWO_BLOCKS;
-        if (two) waves -= TWO_BLOCKS;
-        const int pol = g_kernel_policy.load(std::memory_order_relaxed);
-        if ((pol & 0xff) == 2 && ((pol >> 16) & 0xff)) two = ((pol >> 16) & 0xff) == 2;
-        const int rc = run_chain<T>(OP_UNDELTA_PACK, waves, w, in, bases, out, n, s, nullptr, nullptr, 0, nullptr, two);
+    if (const WaveChoice c = chosen_waves(Elem<T>::BITS, w, WAVE_UNDELTA_PACK); c.waves) {
+        const int rc = run_chain<T>(OP_UNDELTA_PACK, c.waves, w, in, bases, out, n, s, nullptr, nullptr, 0, nullptr, c.two_blocks);
         if (rc >= 0) return rc;                  // -1: no pipeline form of this op (cannot happen today): the cell-column kernel
     }
     return run_stream<T>(unpack_table_impl<T, BODY_UNDELTA>().fn[w], in, out, bases, 0, n, w != 0, true, true, s);
@@ -196,7 +213,7 @@ int dev_undelta_pack_untranspose(unsigned w, const T* in, const T* bases, T* out
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNDELTA_PACK_UNTRANSPOSE)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNDELTA_PACK_UNTRANSPOSE).waves) {
         const int rc = run_chain<T>(OP_UNDELTA_PACK_UNTRANSPOSE, waves, w, in, bases, out, n, s);
         if (rc >= 0) return rc;
     }
@@ -207,7 +224,7 @@ int dev_transpose_delta_pack(unsigned w, const T* in, const T* bases, T* out, si
 {
     if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_TRANSPOSE_DELTA_PACK)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_TRANSPOSE_DELTA_PACK).waves) {
         const int rc = run_chain<T>(OP_TRANSPOSE_DELTA_PACK, waves, w, in, bases, out, n, s);
         if (rc >= 0) return rc;
     }
@@ -220,7 +237,7 @@ int dev_unpack_block_sums(unsigned w, const T* in, size_t n, uint64_t* sums, voi
     if (n == 0) return FL_OK;
     if (!sums || (w != 0 && !in)) return FL_ERR_NULL;
     if (misaligned(in)) return FL_ERR_ALIGN;
-    ReduceArgs a{reinterpret_cast<const u32x4*>(in), sums, nullptr, n, 0, 63};
+    ReduceArgs a{reinterpret_cast<const u32x4*>(in), sums, nullptr, n};
     return hip_status(sum_table_impl<T>().fn[w](a, static_cast<hipStream_t>(s)));
 }
 template <typename T>
@@ -237,8 +254,6 @@ int dev_unpack_compare(unsigned w, const T* in, int op, T constant, size_t n, ui
     a.in = reinterpret_cast<const u32x4*>(in);
     a.mask = reinterpret_cast<u32x4*>(mask);
     a.n_blocks = n;
-    a.tiles_per_xcd = 0;
-    a.window_shift = 63;
     a.is_eq = 0;
     a.invert = 0;
     a.constant = constant;
@@ -254,9 +269,7 @@ int dev_unpack_compare(unsigned w, const T* in, int op, T constant, size_t n, ui
         if (constant == 0) a.constant = MAXV; else { a.constant = (T)(constant - 1); a.invert = 1; }
         break;
     }
-    int waves = compare_launch_waves(Elem<T>::BITS, w);
-    const int pol = g_kernel_policy.load(std::memory_order_relaxed);       // A/B tools: 2 + 256 * waves
-    if ((pol & 0xff) == 2 && ((pol >> 8) & 0xff)) waves = (pol >> 8) & 0xff;
+    const int waves = with_policy({compare_launch_waves(Elem<T>::BITS, w)}).waves;
     return hip_status((a.is_eq ? compare_table_impl<T, true>() : compare_table_impl<T, false>()).fn[w](a, waves, static_cast<hipStream_t>(s)));
 }
 template <typename T>
@@ -265,13 +278,13 @@ int dev_block_min_max(const T* in, size_t n, T* mins, T* maxs, void* s)
     if (n == 0) return FL_OK;
     if (!in || !mins || !maxs) return FL_ERR_NULL;
     if (misaligned(in)) return FL_ERR_ALIGN;
-    ReduceArgs a{reinterpret_cast<const u32x4*>(in), mins, maxs, n, 0, 63};
+    ReduceArgs a{reinterpret_cast<const u32x4*>(in), mins, maxs, n};
     return hip_status(min_max_launcher<T>()(a, static_cast<hipStream_t>(s)));
 }
 template <typename T> int dev_delta(bool inverse, const T* in, const T* bases, T* out, size_t n, void* s)
 {
     if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNDELTA : WAVE_DELTA)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNDELTA : WAVE_DELTA).waves) {
         const int rc = run_chain<T>(inverse ? OP_UNDELTA : OP_DELTA, waves, Elem<T>::BITS, in, bases, out, n, s);
         if (rc >= 0) return rc;
     }
@@ -279,7 +292,7 @@ template <typename T> int dev_delta(bool inverse, const T* in, const T* bases, T
 }
 template <typename T> int dev_transpose(bool inverse, const T* in, T* out, size_t n, void* s)
 {
-    if (const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNTRANSPOSE : WAVE_TRANSPOSE)) {
+    if (const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNTRANSPOSE : WAVE_TRANSPOSE).waves) {
         const int rc = run_chain<T>(inverse ? OP_UNTRANSPOSE : OP_TRANSPOSE, waves, Elem<T>::BITS, in, static_cast<const T*>(nullptr), out, n, s);
         if (rc >= 0) return rc;
     }
@@ -541,20 +554,14 @@ int run_widths(bool pack, const uint8_t* widths, const uint64_t* offsets, const 
     a.refs = with_refs ? refs : nullptr;
     a.ref_stride = ref_stride;
     a.n_blocks = n_blocks;
-    a.tiles_per_xcd = 0;
-    a.window_shift = 63;
     a.uniform_width = 0;
     a.packed_bytes = packed_bytes;
-    a.bpw = mixed_blocks_per_wave(Elem<T>::BITS, pack);
-    a.prefetch = mixed_prefetch(Elem<T>::BITS);
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, pack), mixed_blocks_per_wave(Elem<T>::BITS, pack), mixed_prefetch(Elem<T>::BITS)});
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
     a.linear_map = 0;
     a.nt_from = 0;           // a mixed-width column always streams
-    int waves = mixed_waves(Elem<T>::BITS, pack);
-    const int pol = g_kernel_policy.load(std::memory_order_relaxed);       // A/B tools: 2 + 256*waves + 65536*blocks-per-wavefront (+ 2^24: prefetch)
-    if ((pol & 0xff) == 2 && ((pol >> 8) & 0xff)) waves = (pol >> 8) & 0xff;
-    if ((pol & 0xff) == 2 && ((pol >> 16) & 0xff)) { a.bpw = (pol >> 16) & 0xff; a.prefetch = (pol >> 24) & 1; }
-    if (a.prefetch && (WG / 64) * a.bpw * WaveBlock<T>::BLOCK_BYTES > 64u * 1024u) a.prefetch = 0;   // images would not fit a workgroup's LDS
-    return hip_status(widths_launcher<T>(pack)(a, waves, static_cast<hipStream_t>(stream)));
+    return hip_status(widths_launcher<T>(pack)(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // Delta over a mixed-width column: the pipeline kernel with per-block widths[] / offsets[] on its packed side (fl_chain.hpp)
@@ -564,10 +571,8 @@ int run_chain_widths(int op, const uint8_t* widths, const uint64_t* offsets, con
 {
     if (n_blocks == 0) return FL_OK;
     if (!widths || !offsets) return FL_ERR_NULL;
-    int waves = mixed_waves(Elem<T>::BITS, op == OP_TRANSPOSE_DELTA_PACK);
-    if (sizeof(T) == 1) waves = 0;   // u8 runs the persistent pipelined kernels: 0 = their own grid
-    const int pol = g_kernel_policy.load(std::memory_order_relaxed);       // A/B tools: 2 + 256 * waves
-    if ((pol & 0xff) == 2 && ((pol >> 8) & 0xff)) waves = (pol >> 8) & 0xff;
+    // u8 runs the persistent pipelined kernels: 0 = their own grid
+    const int waves = with_policy({sizeof(T) == 1 ? 0 : mixed_waves(Elem<T>::BITS, op == OP_TRANSPOSE_DELTA_PACK)}).waves;
     const int rc = run_chain<T>(op, waves, 0, in, bases, out, n_blocks, stream, widths, offsets, packed_bytes, err_flag);
     return rc >= 0 ? rc : hip_fail(hipErrorInvalidDeviceFunction);
 }
@@ -596,17 +601,13 @@ int run_batch(bool pack, const void* const* packed, void* const* unpacked, const
     b.refs = with_refs ? refs : nullptr;
     b.bases = nullptr;
     b.n_arrays = n_arrays;
-    b.tiles_per_xcd = 0;
-    b.window_shift = 63;
     b.tiles_per_array = 0;
     b.max_blocks = max_blocks;
-    b.bpw = batch_blocks_per_wave(Elem<T>::BITS, pack);
-    b.prefetch = b.bpw > 1;
-    int waves = batch_waves(Elem<T>::BITS, pack);
-    const int pol = g_kernel_policy.load(std::memory_order_relaxed);       // A/B tools: as for the mixed-width kernels (run_widths)
-    if ((pol & 0xff) == 2 && ((pol >> 8) & 0xff)) waves = (pol >> 8) & 0xff;
-    if ((pol & 0xff) == 2 && ((pol >> 16) & 0xff)) { b.bpw = (pol >> 16) & 0xff; b.prefetch = (pol >> 24) & 1; }
-    return hip_status(batch_launcher<T>(pack)(b, max_blocks, waves, static_cast<hipStream_t>(stream)));
+    const unsigned bpw = batch_blocks_per_wave(Elem<T>::BITS, pack);
+    const WaveShape sh = with_policy({batch_waves(Elem<T>::BITS, pack), bpw, bpw > 1});
+    b.bpw = sh.bpw;
+    b.prefetch = sh.prefetch;
+    return hip_status(batch_launcher<T>(pack)(b, max_blocks, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // Delta over many small arrays (fl_batch.hpp: k_batch_chain)
@@ -628,15 +629,11 @@ int run_batch_chain(int op, const void* const* packed, const void* const* bases,
     b.refs = nullptr;
     b.bases = reinterpret_cast<const char* const*>(bases);
     b.n_arrays = n_arrays;
-    b.tiles_per_xcd = 0;
-    b.window_shift = 63;
     b.tiles_per_array = 0;
     b.max_blocks = max_blocks;
     b.bpw = 1;
     b.prefetch = 0;
-    int waves = mixed_waves(Elem<T>::BITS, op == OP_TRANSPOSE_DELTA_PACK);
-    const int pol = g_kernel_policy.load(std::memory_order_relaxed);       // A/B tools: 2 + 256 * waves
-    if ((pol & 0xff) == 2 && ((pol >> 8) & 0xff)) waves = (pol >> 8) & 0xff;
+    const int waves = with_policy({mixed_waves(Elem<T>::BITS, op == OP_TRANSPOSE_DELTA_PACK)}).waves;
     return hip_status(fn(b, max_blocks, waves, static_cast<hipStream_t>(stream)));
 }
 
@@ -741,8 +738,8 @@ int fl_internal_bare_stream_shape(int op, unsigned type_bits, unsigned width, si
     *out_unit = op == 1 ? packed : unpacked;
     *aux_unit = op == 2 ? 128u * k : 0;
     const WaveOp wop = op == 1 ? WAVE_PACK : op == 2 ? WAVE_UNDELTA_PACK : WAVE_UNPACK;
-    int w = op == 3 ? mixed_waves(type_bits, false) : chosen_waves(type_bits, width, wop);
-    if (w >= TWO_BLOCKS) w -= TWO_BLOCKS;                           // two blocks per wavefront: same bytes per launch, the occupancy is what the table says
+    // two blocks per wavefront: same bytes per launch, the occupancy is what the table says
+    int w = op == 3 ? mixed_waves(type_bits, false) : chosen_waves(type_bits, width, wop).waves;
     if (w == 0) w = 8;       // a cell-column kernel gives a wavefront 8 blocks at 2-3 waves per SIMD: the one-unit-per-wavefront stream needs every slot to keep as many bytes in flight
     *waves = w < 3 ? 3 : w;
     *nt_loads = op == 1 || op == 3 || width >= fl::nt_read_from(type_bits);       // fl_widths.hpp: RD_AUTO; pack reads non-temporally
@@ -783,12 +780,11 @@ int fl_internal_selftune_check(int op, unsigned type_bits, unsigned width, const
     timed(0, *table_ms);
     *best_other_policy = 0;
     const fl::WaveOp wop = op == 1 ? fl::WAVE_PACK : op == 2 ? fl::WAVE_UNDELTA_PACK : fl::WAVE_UNPACK;
-    int tab = fl::wave_policy(type_bits, width, wop);
-    if (tab >= fl::TWO_BLOCKS) tab -= fl::TWO_BLOCKS;
+    const fl::WaveChoice tab = fl::wave_choice(type_bits, width, wop);
     for (int policy : {1, 2 + 256 * 3, 2 + 256 * 4, 2 + 256 * 5, 2 + 256 * 6, 2 + 256 * 8}) {
         if (rc != FL_OK) break;
-        if (policy == 1 && (tab == 0 || !fl::cell_column_built(type_bits, width, wop))) continue;   // the table's own choice, or not built
-        if (policy != 1 && (policy >> 8) == tab && fl::wave_policy(type_bits, width, wop) < fl::TWO_BLOCKS) continue;   // the table's own choice
+        if (policy == 1 && (tab.waves == 0 || !fl::cell_column_built(type_bits, width, wop))) continue;   // the table's own choice, or not built
+        if (policy != 1 && (policy >> 8) == tab.waves && !tab.two_blocks) continue;   // the table's own choice
         float ms = 0.f;
         timed(policy, ms);
         if (rc == FL_OK && ms > 0.f && (*best_other_ms == 0.f || ms < *best_other_ms)) { *best_other_ms = ms; *best_other_policy = policy; }

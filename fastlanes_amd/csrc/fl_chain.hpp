@@ -44,8 +44,8 @@ struct ChainArgs {
     char* out;               // unpacked column (either layout) / packed column
     const char* bases;       // [n_blocks][128 bytes]; unused by CHAIN_NONE
     uint64_t n_blocks;
-    uint64_t tiles_per_xcd;
-    unsigned window_shift;     // tile-map window (fl_kernels.hpp: xcd_tile); filled by the launcher
+    uint64_t tiles_per_xcd = 0;
+    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); both filled by the launcher
     unsigned width;          // SRC_PACKED / SNK_PACKED only
     // mixed-width form of the packed side (SRC_PACKED / SNK_PACKED only; fl_widths.hpp's surface): block b has widths[b] and its
     // 128*widths[b] bytes start at byte offsets[b] of the packed column.  nullptr = every block has `width`, back to back.
@@ -534,19 +534,11 @@ hipError_t launch_chain(const ChainArgs& a0, int waves, hipStream_t s)
     if (a0.n_blocks == 0) return hipSuccess;
     ChainArgs a = a0;
     constexpr unsigned TILE_BLOCKS = BPW * (WG / 64);
-    const uint64_t n_tiles = (a.n_blocks + TILE_BLOCKS - 1) / TILE_BLOCKS;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (a.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;
-    a.window_shift = tile_window_shift(chain_window_op<SRC, BODY, SNK>(), WaveBlock<T>::TB, TILE_BLOCKS);
-    if constexpr (SRC == SRC_PACKED || SNK == SNK_PACKED) {
-        if (a.widths) a.window_shift |= TILE_MAP_ROTATE;     // per-block widths may be periodic (fl_widths.hpp: launch_widths)
-    } else {
-        a.widths = nullptr;
-    }
-    const unsigned need = TILE_BLOCKS * chain_wave_lds<T, SRC, SNK>();
-    if (waves < 3) waves = 3;
-    const unsigned pad = (CU_LDS_BYTES * (unsigned)WG / ((unsigned)waves * 256u)) & ~1023u;
-    FL_LAUNCH((k_chain<T, SRC, BODY, SNK, RD, BPW>), dim3((unsigned)(a.tiles_per_xcd * 8)), dim3(WG), pad > need ? pad : need, s, a);
+    if constexpr (SRC != SRC_PACKED && SNK != SNK_PACKED) a.widths = nullptr;
+    // per-block widths may be periodic: rotated (fl_widths.hpp: launch_widths)
+    const unsigned grid = plan_blocks(a, a.n_blocks, TILE_BLOCKS, chain_window_op<SRC, BODY, SNK>(), WaveBlock<T>::TB, a.widths != nullptr);
+    if (!grid) return hipErrorInvalidValue;
+    FL_LAUNCH((k_chain<T, SRC, BODY, SNK, RD, BPW>), dim3(grid), dim3(WG), occupancy_lds(waves, TILE_BLOCKS * chain_wave_lds<T, SRC, SNK>()), s, a);
     return hipGetLastError();
 }
 
@@ -864,13 +856,10 @@ hipError_t launch_chain_columns_pipelined(const ChainArgs& a0, int waves, hipStr
     const int per_cu_override = waves > 0 ? 4 * waves : COLUMNS_WAVES_PER_CU;
     ChainArgs a = a0;
     constexpr unsigned TILE_BLOCKS = COLUMN_LANES_BPW;
-    const uint64_t n_tiles = (a.n_blocks + TILE_BLOCKS - 1) / TILE_BLOCKS;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (a.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;
-    a.window_shift = tile_window_shift(SNK == SNK_ORIGINAL ? WIN_UNDELTA_PACK_UNTRANSPOSE : WIN_UNDELTA_PACK, WaveBlock<T>::TB, TILE_BLOCKS);
-    if (a.widths) a.window_shift |= TILE_MAP_ROTATE;
+    unsigned grid = plan_blocks(a, a.n_blocks, TILE_BLOCKS, SNK == SNK_ORIGINAL ? WIN_UNDELTA_PACK_UNTRANSPOSE : WIN_UNDELTA_PACK, WaveBlock<T>::TB,
+                                a.widths != nullptr);
+    if (!grid) return hipErrorInvalidValue;
     const unsigned lds = TILE_BLOCKS * (SNK == SNK_ORIGINAL && sizeof(T) == 1 ? ORIGINAL_U8_STRIDE : WaveBlock<T>::BLOCK_BYTES);
-    unsigned grid = (unsigned)(a.tiles_per_xcd * 8);
     if (hipError_t e = persistent_grid<k_chain_columns_pipelined<T, SNK>>(lds, per_cu_override, grid); e != hipSuccess) return e;
     FL_LAUNCH((k_chain_columns_pipelined<T, SNK>), dim3(grid), dim3(64), lds, s, a);
     return hipGetLastError();
@@ -1053,13 +1042,9 @@ hipError_t launch_chain_columns_encode_pipelined(const ChainArgs& a0, int waves,
     if (a0.n_blocks == 0) return hipSuccess;
     ChainArgs a = a0;
     constexpr unsigned TILE_BLOCKS = COLUMN_LANES_BPW;
-    const uint64_t n_tiles = (a.n_blocks + TILE_BLOCKS - 1) / TILE_BLOCKS;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (a.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;
-    a.window_shift = tile_window_shift(WIN_TRANSPOSE_DELTA_PACK, WaveBlock<T>::TB, TILE_BLOCKS);
-    if (a.widths) a.window_shift |= TILE_MAP_ROTATE;
+    unsigned grid = plan_blocks(a, a.n_blocks, TILE_BLOCKS, WIN_TRANSPOSE_DELTA_PACK, WaveBlock<T>::TB, a.widths != nullptr);
+    if (!grid) return hipErrorInvalidValue;
     const unsigned lds = TILE_BLOCKS * ORIGINAL_U8_STRIDE;
-    unsigned grid = (unsigned)(a.tiles_per_xcd * 8);
     if (hipError_t e = persistent_grid<k_chain_columns_encode_pipelined<T>>(lds, waves > 0 ? 4 * waves : COLUMNS_WAVES_PER_CU, grid); e != hipSuccess) return e;
     FL_LAUNCH((k_chain_columns_encode_pipelined<T>), dim3(grid), dim3(64), lds, s, a);
     return hipGetLastError();

@@ -29,8 +29,8 @@ struct ReduceArgs {
     void* out0;            // sums (uint64 per block) or mins (T per block)
     void* out1;            // maxs (T per block) or unused
     uint64_t n_blocks;
-    uint64_t tiles_per_xcd;
-    unsigned window_shift;  // tile-map window (fl_kernels.hpp: xcd_tile)
+    uint64_t tiles_per_xcd = 0;
+    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); both filled by the launcher
 };
 
 __device__ __forceinline__ bool tile_of_workgroup(const ReduceArgs& a, uint64_t& tile)
@@ -183,8 +183,8 @@ struct CompareArgs {
     uint32_t is_eq;        // 1: x == k, 0: x <= k (selects the kernel instance on the host)
     uint32_t invert;       // complement the result
     uint64_t n_blocks;
-    uint64_t tiles_per_xcd;
-    unsigned window_shift;  // tile-map window (fl_kernels.hpp: xcd_tile)
+    uint64_t tiles_per_xcd = 0;
+    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); both filled by the launcher
 };
 
 // u8 / u16 compare SWAR-wise: all elements of a 32-bit word at once, the verdict of an element landing in ONE bit of its
@@ -530,13 +530,13 @@ template <typename T, int W, bool IS_EQ> hipError_t launch_unpack_compare(const 
 {
     if (a0.n_blocks == 0) return hipSuccess;
     CompareArgs a = a0;
-    const uint64_t n_tiles = (a.n_blocks + BLOCKS_PER_WG - 1) / BLOCKS_PER_WG;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    a.window_shift = tile_window_shift(WIN_UNPACK_COMPARE, Elem<T>::BITS, BLOCKS_PER_WG);
+    const unsigned grid = plan_blocks(a, a.n_blocks, BLOCKS_PER_WG, WIN_UNPACK_COMPARE, Elem<T>::BITS);
+    if (!grid) return hipErrorInvalidValue;
+    // not occupancy_lds: the kernel's static LDS counts against the CU's, and the figure does not scale with WG (A/B builds)
     constexpr unsigned STATIC_LDS = sizeof(T) >= 4 ? 0u : BLOCKS_PER_WG * 144u;
     unsigned pad = 0;
-    if (waves >= 3 && waves < 8) pad = ((160u * 1024u / (unsigned)waves) & ~1023u) - STATIC_LDS;   // < 64 KiB for waves >= 3
-    FL_LAUNCH((k_unpack_compare<T, W, IS_EQ>), dim3((unsigned)(a.tiles_per_xcd * 8)), dim3(WG), pad, s, a);
+    if (waves >= 3 && waves < 8) pad = ((CU_LDS_BYTES / (unsigned)waves) & ~1023u) - STATIC_LDS;   // < 64 KiB for waves >= 3
+    FL_LAUNCH((k_unpack_compare<T, W, IS_EQ>), dim3(grid), dim3(WG), pad, s, a);
     return hipGetLastError();
 }
 template <typename T> struct CompareTable { compare_launch_t fn[Elem<T>::BITS + 1]; };
@@ -550,18 +550,12 @@ template <typename T, bool IS_EQ> const CompareTable<T>& compare_table_impl();
 
 typedef hipError_t (*reduce_launch_t)(const ReduceArgs&, hipStream_t);
 
-inline unsigned plan_grid(ReduceArgs& a, WindowOp op, unsigned type_bits)
-{
-    const uint64_t n_tiles = (a.n_blocks + BLOCKS_PER_WG - 1) / BLOCKS_PER_WG;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    a.window_shift = tile_window_shift(op, type_bits, BLOCKS_PER_WG);
-    return (unsigned)(a.tiles_per_xcd * 8);
-}
 template <typename T, int W> hipError_t launch_unpack_block_sums(const ReduceArgs& a0, hipStream_t s)
 {
     if (a0.n_blocks == 0) return hipSuccess;
     ReduceArgs a = a0;
-    const unsigned grid = plan_grid(a, WIN_UNPACK_BLOCK_SUMS, Elem<T>::BITS);
+    const unsigned grid = plan_blocks(a, a.n_blocks, BLOCKS_PER_WG, WIN_UNPACK_BLOCK_SUMS, Elem<T>::BITS);
+    if (!grid) return hipErrorInvalidValue;
     FL_LAUNCH((k_unpack_block_sums<T, W>), dim3(grid), dim3(WG), 0, s, a);
     return hipGetLastError();
 }
@@ -569,7 +563,8 @@ template <typename T> hipError_t launch_block_min_max(const ReduceArgs& a0, hipS
 {
     if (a0.n_blocks == 0) return hipSuccess;
     ReduceArgs a = a0;
-    const unsigned grid = plan_grid(a, WIN_BLOCK_MIN_MAX, Elem<T>::BITS);
+    const unsigned grid = plan_blocks(a, a.n_blocks, BLOCKS_PER_WG, WIN_BLOCK_MIN_MAX, Elem<T>::BITS);
+    if (!grid) return hipErrorInvalidValue;
     FL_LAUNCH((k_block_min_max<T>), dim3(grid), dim3(WG), 0, s, a);
     return hipGetLastError();
 }

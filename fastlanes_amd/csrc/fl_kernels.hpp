@@ -36,8 +36,8 @@ struct StreamArgs {
     const void* aux;       // references [n_blocks*aux_stride] or bases [n_blocks][LANES]
     uint64_t aux_stride;   // FoR: 0 = one scalar for all blocks, 1 = one per block
     uint64_t n_blocks;
-    uint64_t tiles_per_xcd;   // ceil(ceil(n_blocks/32) / 8)
-    unsigned window_shift;    // log2 of the tile-map window in tiles (>= 32: one window = the whole column) [| TILE_MAP_ROTATE]; see xcd_tile
+    uint64_t tiles_per_xcd = 0;   // ceil(ceil(n_blocks/32) / 8)
+    unsigned window_shift = 63;   // log2 of the tile-map window in tiles (>= 32: one window = the whole column) [| TILE_MAP_ROTATE]; see xcd_tile
 };
 
 // The XCD-aware tile map shared by every kernel: workgroup b -> tile.  The grid is 8 * tiles_per_xcd workgroups (a multiple
@@ -62,7 +62,7 @@ template <typename U> __device__ __forceinline__ U rotate_rows_of_32(U r, U run,
 }
 template <typename U = uint64_t> __device__ __forceinline__ U xcd_tile(unsigned b, U tiles_per_xcd, unsigned window_shift_and_flags)
 {
-    // a window is a multiple of 8 tiles: anything below 2^3 (a launcher that skipped plan_grid / tile_window_shift) is taken as 2^3,
+    // a window is a multiple of 8 tiles: anything below 2^3 (a launcher that skipped plan_tiles / tile_window_shift) is taken as 2^3,
     // or several workgroups would map to one tile and others to none
     const unsigned window_shift = (window_shift_and_flags & 0x7fu) < 3u ? 3u : (window_shift_and_flags & 0x7fu);
     const bool rotate = (window_shift_and_flags & TILE_MAP_ROTATE) != 0;
@@ -95,17 +95,46 @@ inline bool& constructed_pair_this_thread()
     static thread_local bool v = false;
     return v;
 }
-// window_shift of a launch: the (op, type)'s window from the generated table (or the override) in blocks -> tiles of `tile_blocks` blocks
+// window_shift of a window of 2^log2_blocks blocks (>= WINDOW_WHOLE: the whole column) in tiles of `tile_blocks` blocks
+inline unsigned window_shift_of(int log2_blocks, unsigned tile_blocks)
+{
+    if (log2_blocks >= WINDOW_WHOLE) return 63u;
+    int tl = 0;
+    while ((2u << tl) <= tile_blocks) ++tl;                  // floor(log2(tile_blocks))
+    const int sh = log2_blocks - tl;
+    return (unsigned)(sh < 3 ? 3 : sh);                      // a window is a multiple of 8 tiles
+}
+// window_shift of a launch: the (op, type)'s window from the generated table (or the override)
 inline unsigned tile_window_shift(WindowOp op, unsigned type_bits, unsigned tile_blocks)
 {
     const int mine = window_override_this_thread();
     const int ov = mine ? mine : window_override().load(std::memory_order_relaxed);
-    const int lg = ov ? ov : constructed_pair_this_thread() ? (int)WINDOW_WHOLE : window_log2_blocks(op, type_bits);
-    if (lg >= WINDOW_WHOLE) return 63u;
-    int tl = 0;
-    while ((2u << tl) <= tile_blocks) ++tl;                  // floor(log2(tile_blocks))
-    const int sh = lg - tl;
-    return (unsigned)(sh < 3 ? 3 : sh);                      // a window is a multiple of 8 tiles
+    return window_shift_of(ov ? ov : constructed_pair_this_thread() ? (int)WINDOW_WHOLE : window_log2_blocks(op, type_bits), tile_blocks);
+}
+
+// THE LAUNCH PLAN of every kernel on the tile map: n_tiles tiles -> a grid of 8 XCD slots x tiles_per_xcd workgroups (padding
+// workgroups exit at once), walked in windows of 2^window_shift tiles.  Fills the argument block's tile-map fields and returns the
+// grid, or 0 past 2^31 workgroups (more than 2^33 blocks: no allocation on the card holds them), which a launcher refuses.
+template <typename Args> inline unsigned plan_tiles(Args& a, uint64_t n_tiles, unsigned window_shift)
+{
+    a.tiles_per_xcd = (n_tiles + 7) / 8;
+    a.window_shift = window_shift;
+    return a.tiles_per_xcd * 8 > 0x7fffffffull ? 0u : (unsigned)(a.tiles_per_xcd * 8);
+}
+// ... of n_blocks blocks in tiles of tile_blocks, in the (op, type)'s window; rotate: TILE_MAP_ROTATE (the mixed-width kernels)
+template <typename Args>
+inline unsigned plan_blocks(Args& a, uint64_t n_blocks, unsigned tile_blocks, WindowOp op, unsigned type_bits, bool rotate = false)
+{
+    return plan_tiles(a, (n_blocks + tile_blocks - 1) / tile_blocks, tile_window_shift(op, type_bits, tile_blocks) | (rotate ? TILE_MAP_ROTATE : 0u));
+}
+// Occupancy as a launch parameter: the dynamic-LDS request with which `waves` workgroups per CU (= waves per SIMD at WG = 256) share
+// its 160 KiB, waves >= 3 (53 KiB per workgroup: below the 64 KiB default dynamic-LDS limit) -- or the kernel's own `need`, if more
+constexpr unsigned CU_LDS_BYTES = 160 * 1024;
+inline unsigned occupancy_lds(int waves, unsigned need = 0)
+{
+    if (waves < 3) waves = 3;
+    const unsigned pad = (CU_LDS_BYTES * (unsigned)WG / ((unsigned)waves * 256u)) & ~1023u;
+    return pad > need ? pad : need;
 }
 
 // ---------------------------------------------------------------------------
@@ -396,14 +425,11 @@ void k_delta(StreamArgs a)
 // ---------------------------------------------------------------------------
 typedef hipError_t (*stream_launch_t)(const StreamArgs&, hipStream_t);
 
-// grid = 8 XCD slots x tiles_per_xcd (padding workgroups exit immediately)
-// (user kernels on the functor API: plan_grid(a) = the whole-column map; plan_grid MUST fill the launch's tile-map fields)
+// plan_tiles for the cell-column kernels: tiles of BLOCKS_PER_WG blocks, the (op, type)'s window
+// (user kernels on the functor API: plan_grid(a) = the whole-column map; plan_grid MUST fill the launch's tile-map fields; 0 = too large)
 inline unsigned plan_grid(StreamArgs& a, WindowOp op = WIN_TRANSPOSE, unsigned type_bits = 0)
 {
-    const uint64_t n_tiles = (a.n_blocks + BLOCKS_PER_WG - 1) / BLOCKS_PER_WG;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    a.window_shift = type_bits ? tile_window_shift(op, type_bits, BLOCKS_PER_WG) : 63u;
-    return (unsigned)(a.tiles_per_xcd * 8);
+    return plan_tiles(a, (a.n_blocks + BLOCKS_PER_WG - 1) / BLOCKS_PER_WG, type_bits ? tile_window_shift(op, type_bits, BLOCKS_PER_WG) : 63u);
 }
 
 template <typename T, int W, int BODY>
@@ -412,6 +438,7 @@ hipError_t launch_unpack(const StreamArgs& a0, hipStream_t s)
     if (a0.n_blocks == 0) return hipSuccess;
     StreamArgs a = a0;
     const unsigned grid = plan_grid(a, BODY == BODY_UNDELTA ? WIN_UNDELTA_PACK : BODY == BODY_UNDELTA_UNTRANSPOSE ? WIN_UNDELTA_PACK_UNTRANSPOSE : WIN_UNPACK, Elem<T>::BITS);
+    if (!grid) return hipErrorInvalidValue;
     FL_LAUNCH((k_unpack<T, W, BODY>), dim3(grid), dim3(WG), 0, s, a);
     return hipGetLastError();
 }
@@ -421,6 +448,7 @@ hipError_t launch_pack(const StreamArgs& a0, hipStream_t s)
     if (a0.n_blocks == 0 || W == 0) return hipSuccess;
     StreamArgs a = a0;
     const unsigned grid = plan_grid(a, MODE == PACK_TRANSPOSE_DELTA ? WIN_TRANSPOSE_DELTA_PACK : WIN_PACK, Elem<T>::BITS);
+    if (!grid) return hipErrorInvalidValue;
     FL_LAUNCH((k_pack<T, W, MODE>), dim3(grid), dim3(WG), 0, s, a);
     return hipGetLastError();
 }
@@ -430,6 +458,7 @@ hipError_t launch_delta(const StreamArgs& a0, hipStream_t s)
     if (a0.n_blocks == 0) return hipSuccess;
     StreamArgs a = a0;
     const unsigned grid = plan_grid(a, INVERSE ? WIN_UNDELTA : WIN_DELTA, Elem<T>::BITS);
+    if (!grid) return hipErrorInvalidValue;
     FL_LAUNCH((k_delta<T, INVERSE>), dim3(grid), dim3(WG), 0, s, a);
     return hipGetLastError();
 }

@@ -16,9 +16,9 @@ struct BareArgs {
     const char* aux;
     char* out;
     uint64_t n_units;
-    uint64_t tiles_per_xcd;
+    uint64_t tiles_per_xcd = 0;
     unsigned in_unit, aux_unit, out_unit;    // bytes per unit, each a multiple of 16 and <= 8192 (aux_unit <= 1024)
-    unsigned window_shift;
+    unsigned window_shift = 63;              // filled by the launcher, as tiles_per_xcd
 };
 
 constexpr unsigned BARE_MAX_UNIT = 8192;
@@ -58,16 +58,12 @@ inline hipError_t launch_bare_stream(BareArgs a, bool nt_loads, int waves, int w
     if (a.n_units == 0) return hipSuccess;
     if (a.in_unit > BARE_MAX_UNIT || a.out_unit > BARE_MAX_UNIT || a.aux_unit > 1024u || ((a.in_unit | a.out_unit | a.aux_unit) & 15u))
         return hipErrorInvalidValue;
-    const uint64_t n_tiles = (a.n_units + (WG / 64) - 1) / (WG / 64);
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (a.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;
-    if (window_log2_units >= WINDOW_WHOLE || window_log2_units <= 0) a.window_shift = 63u;
-    else a.window_shift = (unsigned)(window_log2_units - 2 < 3 ? 3 : window_log2_units - 2);       // tiles of 4 units
-    if (waves < 3) waves = 3;
-    if (waves > 8) waves = 8;
-    const unsigned lds = (CU_LDS_BYTES * (unsigned)WG / ((unsigned)waves * 256u)) & ~1023u;                                 // workgroups per CU = waves per SIMD
-    if (nt_loads) FL_LAUNCH((k_bare_stream<true>), dim3((unsigned)(a.tiles_per_xcd * 8)), dim3(WG), lds, s, a);
-    else FL_LAUNCH((k_bare_stream<false>), dim3((unsigned)(a.tiles_per_xcd * 8)), dim3(WG), lds, s, a);
+    // the window in tiles of 4 units whatever WG is (A/B builds: as it always was)
+    const unsigned grid = plan_tiles(a, (a.n_units + (WG / 64) - 1) / (WG / 64), window_log2_units <= 0 ? 63u : window_shift_of(window_log2_units, 4));
+    if (!grid) return hipErrorInvalidValue;
+    const unsigned lds = occupancy_lds(waves > 8 ? 8 : waves);                                 // workgroups per CU = waves per SIMD
+    if (nt_loads) FL_LAUNCH((k_bare_stream<true>), dim3(grid), dim3(WG), lds, s, a);
+    else FL_LAUNCH((k_bare_stream<false>), dim3(grid), dim3(WG), lds, s, a);
     return hipGetLastError();
 }
 

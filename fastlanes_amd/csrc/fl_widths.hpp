@@ -37,13 +37,13 @@ struct WidthsArgs {
     const void* refs;          // FoR: references[b * ref_stride] (ffor.rs:24-50); nullptr = plain BitPacking
     uint64_t ref_stride;
     uint64_t n_blocks;
-    uint64_t tiles_per_xcd;
+    uint64_t tiles_per_xcd = 0;  // filled by the launcher
     unsigned uniform_width;
     unsigned bpw;              // consecutive blocks per wavefront (>= 1); a workgroup takes 4*bpw blocks
     uint64_t packed_bytes;     // size of the packed column: a block must lie inside [0, packed_bytes) (only read when widths != nullptr)
     unsigned prefetch;         // bpw > 1: 1 = request all bpw blocks of the wavefront up front by LDS-DMA (one LDS image per block)
     unsigned linear_map;       // A/B tools: 1 = workgroup b takes tile b instead of the XCD-contiguous map
-    unsigned window_shift;     // tile-map window (fl_kernels.hpp: xcd_tile); filled by the launcher
+    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); filled by the launcher
     unsigned nt_from;          // RD_AUTO: uniform widths >= this stream non-temporally by LDS-DMA (fl_dispatch.hpp: nt_read_from)
 };
 
@@ -710,13 +710,13 @@ typedef hipError_t (*widths_launch_t)(const WidthsArgs&, int waves, hipStream_t)
 // prefetch of the next block measured 1-5 % slower, the round-1 bucketed plan kernel 5-10 % slower; a bare 33:64
 // read:write stream of the same bytes reaches 6.23-6.53 TB/s where this kernel reaches 6.37-6.66.  The shipped
 // occupancy / blocks-per-wavefront per type live in fl_dispatch.hpp (mixed_waves, mixed_blocks_per_wave).
-constexpr unsigned CU_LDS_BYTES = 160 * 1024;
-template <typename T> inline unsigned widths_lds_bytes(int waves, unsigned images_per_wave = 1)
+// The launchers of these kernels and of fl_batch.hpp's k_batch take bpw / prefetch as given, tidied here: bpw >= 1, and prefetch
+// only for 2..16 blocks whose images fit a workgroup's 64 KiB.  Returns the LDS the workgroup's block images need.
+template <typename T> inline unsigned tidy_wave_blocks(unsigned& bpw, unsigned& prefetch)
 {
-    const unsigned need = (WG / 64) * WaveBlock<T>::BLOCK_BYTES * images_per_wave;
-    if (waves < 3) waves = 3;                     // 53 KiB per workgroup: stays below the 64 KiB default dynamic-LDS limit
-    unsigned pad = (CU_LDS_BYTES * (unsigned)WG / ((unsigned)waves * 256u)) & ~1023u;
-    return pad > need ? pad : need;
+    if (bpw == 0) bpw = 1;
+    if (bpw < 2 || bpw > 16 || (WG / 64) * bpw * WaveBlock<T>::BLOCK_BYTES > 64u * 1024u) prefetch = 0;
+    return (WG / 64) * WaveBlock<T>::BLOCK_BYTES * (prefetch ? bpw : 1u);
 }
 
 template <typename T, bool PACK, int RD = (PACK ? RD_VGPR : RD_AUTO)>
@@ -724,19 +724,13 @@ hipError_t launch_widths(const WidthsArgs& a0, int waves, hipStream_t s)
 {
     if (a0.n_blocks == 0) return hipSuccess;
     WidthsArgs a = a0;
-    if (a.bpw == 0) a.bpw = 1;
-    const uint64_t tile_blocks = (uint64_t)a.bpw * (WG / 64);
-    const uint64_t n_tiles = (a.n_blocks + tile_blocks - 1) / tile_blocks;
-    a.tiles_per_xcd = (n_tiles + 7) / 8;
-    if (a.tiles_per_xcd * 8 > 0x7fffffffull) return hipErrorInvalidValue;   // > 2^33 blocks in one launch
-    a.window_shift = tile_window_shift(PACK ? WIN_PACK : WIN_UNPACK, WaveBlock<T>::TB, (unsigned)tile_blocks);
-    if (a.widths) a.window_shift |= TILE_MAP_ROTATE;         // per-block widths may be periodic: keep CUs from locking onto one phase
-    const dim3 grid((unsigned)(a.tiles_per_xcd * 8));
-    if (a.bpw < 2 || a.bpw > 16) a.prefetch = 0;
-    const unsigned lds = widths_lds_bytes<T>(waves, a.prefetch ? a.bpw : 1u);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;         // beyond the default dynamic-LDS limit
-    if constexpr (PACK) FL_LAUNCH((k_pack_widths<T, RD>), grid, dim3(WG), lds, s, a);
-    else FL_LAUNCH((k_unpack_widths<T, RD>), grid, dim3(WG), lds, s, a);
+    const unsigned need = tidy_wave_blocks<T>(a.bpw, a.prefetch);
+    // per-block widths may be periodic: TILE_MAP_ROTATE keeps CUs from locking onto one phase
+    const unsigned grid = plan_blocks(a, a.n_blocks, a.bpw * (WG / 64), PACK ? WIN_PACK : WIN_UNPACK, WaveBlock<T>::TB, a.widths != nullptr);
+    const unsigned lds = occupancy_lds(waves, need);
+    if (!grid || lds > 64 * 1024) return hipErrorInvalidValue;         // > 2^33 blocks; beyond the default dynamic-LDS limit
+    if constexpr (PACK) FL_LAUNCH((k_pack_widths<T, RD>), dim3(grid), dim3(WG), lds, s, a);
+    else FL_LAUNCH((k_unpack_widths<T, RD>), dim3(grid), dim3(WG), lds, s, a);
     return hipGetLastError();
 }
 
