@@ -12,6 +12,12 @@ on the data path): weak scaling, value = N * 10.24 G integers / max-over-ranks t
 `python -m torch.distributed.run ... bench.py --gpus N` it is one of the N ranks.
 Either way rank 0 prints ONE JSON line.
 
+A plain run does only what its headline needs: it sets up (buffers placed and filled), warms up, times the K steps,
+writes --dump-outputs if asked, and prints the line.  Everything else described below -- the oracle checks, the bare
+stream, dispatch_check, live PMC traffic, cpu_baseline and the config5_strong leg -- runs with --full.  The one
+exception: --dump-outputs writes the config5_strong leg's outputs in a plain run too, so that leg is set up, warmed
+up and timed there only to write them.
+
 Control plane (barrier, max-over-ranks time, gather of per-rank figures -- the data
 path has NO collective): a gloo group always exists; RCCL ("nccl") is tried on top of
 it -- first in a throw-away child process per rank (a hang or crash there costs a
@@ -19,7 +25,7 @@ timeout, not the run), then in-process -- and used for the barrier / reductions 
 EVERY rank got it working; otherwise the run continues on gloo.  The line says which
 (`control_backend`, `control_fallback_reason`).
 
-Every rank checks what it just timed, both legs, outside the timed region: the first and
+With --full every rank checks what it just timed, both legs, outside the timed region: the first and
 last block of ITS slice plus sampled blocks byte for byte against the oracle, then
 (--verify full, the default) EVERY block of its slice -- two 64-bit content hashes per
 block computed on the device against the multithreaded CPU oracle decoding the same
@@ -33,18 +39,19 @@ allocates every layout it knows -- the one it CONSTRUCTS from measured 1-GiB chu
 (FL_LAYOUT_INTERLEAVED, round 6), plain allocations, the 64-GiB-zoned slab --, times a bare
 stream of the pair's read : write proportion on each before anything is filled, keeps the
 fastest pair and reports every figure (`roofline.placement_probe_GBps`) -- figures any user of
-the header can reproduce.  After
+the header can reproduce.  With --full, after
 the checks a BARE STREAM of the workload's exact read : write mix is timed on the workload's
 own buffers (`roofline.bare_stream_GBps`, `roofline.frac_of_bare_stream`): box and
 placement cancel in that ratio, the kernel stays.
 
-After the headline leg the same processes time BASELINE.json configs[4] --
+With --full, after the headline leg the same processes time BASELINE.json configs[4] --
 u32, width[b] = 1 + b mod 32, the 10 B-integer column (9 765 625 blocks) sharded
 by contiguous block range over the N GPUs, widths / offsets device-resident --
 and report it STRONG-scaled under "config5_strong" (per-rank GB/s included).
 
 The line also carries `roofline` (live HIP-event timing of the kernel vs the
-8 TB/s HBM peak, PMC traffic) and, at N=1, `cpu_baseline` (the oracle's
+8 TB/s HBM peak; HBM traffic from live PMC passes with --full, else from the committed
+profiles/pmc_traffic.json) and, with --full at N=1, `cpu_baseline` (the oracle's
 auto-vectorised C restatement of the reference's scalar loop, timed on this
 box's host cores on a bounded sample).
 
@@ -105,6 +112,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=10_000_000, help="1024-value blocks per GPU")
     ap.add_argument("--workload", default="u32_w7_unpack", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle checks, bare stream, dispatch_check, live PMC traffic, cpu_baseline and the "
+                         "config5_strong leg (a plain run sets up, warms up, times the steps, dumps if asked and prints the line); "
+                         "the --no-* options, --cpu-seconds and --verify below apply to a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="CPU baseline time budget per leg")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes (roofline.traffic "
@@ -133,7 +144,7 @@ def parse():
                          "(decode workloads) or a device-side round trip of the whole slice (pack); auto = full")
     ap.add_argument("--probe-nccl", action="store_true", help="with --dry-run: still attempt the RCCL probe (exercises the "
                     "fallback on a box without GPUs)")
-    ap.add_argument("--inject-mismatch", type=int, default=-1, help="with --dry-run: pretend this rank's oracle check failed "
+    ap.add_argument("--inject-mismatch", type=int, default=-1, help="with --dry-run --full: pretend this rank's oracle check failed "
                     "(tests that one bad rank fails the whole launch)")
     ap.add_argument("--nccl-probe-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--nccl-probe-timeout", type=float, default=120.0, help="seconds the throw-away RCCL probe may take")
@@ -931,7 +942,8 @@ def placed_workload(name, n, first, rank, dev, args, single_device=False):
 def config5_leg(args, world, rank, dev, ctl):
     """BASELINE.json configs[4], STRONG scaling: the 10 B-integer u32 column (9 765 625 blocks, width[b] = 1 + b mod 32)
     sharded by contiguous block range over the ranks (no collective on the data path).  `w` = this rank's slice, already
-    resident in HBM (main() builds both legs' columns before anything is timed)."""
+    resident in HBM (main() builds both legs' columns before anything is timed).
+    Without --full it runs only to write its --dump-outputs files: set up, warm up, time, dump, release, return None."""
     from fastlanes_amd.sharding import block_range
     first, n = block_range(CONFIG5_BLOCKS, world, rank)
     if args.dry_run:
@@ -942,6 +954,9 @@ def config5_leg(args, world, rank, dev, ctl):
     elapsed, kern_ms = timed_region(w.step, args, ctl)
     if args.dump_outputs:
         dump_outputs(w, "config5_strong", first, args, world, rank)
+    if not args.full:
+        release(w)
+        return None
     avg_ms = sum(kern_ms) / len(kern_ms)
     per_rank = ctl.gather([float(n), avg_ms, float(w.bytes)])
     flags, n_checked, verified = run_check(w, args, ctl)
@@ -1029,14 +1044,16 @@ def main():
         ctl.barrier()
         ctl.all_max(time.perf_counter() - t0)
         per_rank = ctl.gather([float(rank), float(n)])
-        flags = [bool(v[0]) for v in ctl.gather([0.0 if rank == args.inject_mismatch else 1.0])]   # the verdict plumbing
-        c5 = None if (args.no_config5 or strong_main) else config5_leg(args, world, rank, dev, ctl)
+        flags = []
+        if args.full:                    # the verdict plumbing of the checks
+            flags = [bool(v[0]) for v in ctl.gather([0.0 if rank == args.inject_mismatch else 1.0])]
+        c5 = config5_leg(args, world, rank, dev, ctl) if args.full and not (args.no_config5 or strong_main) else None
         if rank == 0:
             print(json.dumps(dict({"metric": "DRY RUN (no GPU work): launcher / rendezvous / sharding plumbing only",
                                    "value": None, "unit": "Gint/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                                   "dry_run": True, "ranks": [int(v[0]) for v in per_rank],
+                                   "dry_run": True, "full": args.full, "ranks": [int(v[0]) for v in per_rank],
                                    "blocks_per_rank": [int(v[1]) for v in per_rank], "config5_strong": c5,
-                                   "per_rank": [{"rank": r, "correct": f} for r, f in enumerate(flags)],
+                                   "per_rank": [dict({"rank": r}, **({"correct": flags[r]} if flags else {})) for r in range(world)],
                                    "correctness": check_text(flags, 0)}, **control)), flush=True)
         ctl.close()
         if not all(flags):
@@ -1052,20 +1069,22 @@ def main():
         dump_outputs(w, args.workload, first, args, world, rank)
     avg_ms = sum(kern_ms) / len(kern_ms)
     per_rank = ctl.gather([float(n), avg_ms, float(w.bytes)])
-    flags, n_checked, verified = run_check(w, args, ctl)       # every rank, its own slice, outside the timed region
     placed, classes = w.placement, getattr(w, "classes", "")
-    bare = bare_stream(w) if rank == 0 else None     # after the checks (it overwrites the output), same buffers, same run
-    tune = None
-    if rank == 0 and world == 1 and not args.no_dispatch_check:
-        try:
-            tune = dispatch_check(w, gib=8.0)
-        except Exception as e:                       # measurement tooling must never take the bench line down
-            print(f"dispatch_check failed: {e!r}", file=sys.stderr)
-    release(w)                                       # leg 1 is measured and checked: its column can go
+    flags, n_checked, verified = [], 0, []
+    bare = tune = None
+    if args.full:
+        flags, n_checked, verified = run_check(w, args, ctl)       # every rank, its own slice, outside the timed region
+        bare = bare_stream(w) if rank == 0 else None     # after the checks (it overwrites the output), same buffers, same run
+        if rank == 0 and world == 1 and not args.no_dispatch_check:
+            try:
+                tune = dispatch_check(w, gib=8.0)
+            except Exception as e:                       # measurement tooling must never take the bench line down
+                print(f"dispatch_check failed: {e!r}", file=sys.stderr)
+    release(w)                                       # leg 1 is measured (and with --full checked): its column can go
 
-    # ---- rank 0, N=1: the cpu_baseline leg (with the checks, the only place bench.py touches oracle/)
+    # ---- rank 0, N=1, --full: the cpu_baseline leg (with the checks, the only place bench.py touches oracle/)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, ty, width, op)
 
     out = None
@@ -1073,7 +1092,7 @@ def main():
         ints = CONFIG5_BLOCKS * 1024 if strong_main else n * 1024 * world
         value = ints * args.steps / elapsed / 1e9
         traffic = traffic_source = None
-        if world == 1 and not args.no_pmc:
+        if args.full and world == 1 and not args.no_pmc:
             live = live_pmc_traffic(args)
             if live is not None:
                 traffic = int(live["bytes"])
@@ -1122,6 +1141,7 @@ def main():
             "config": {"workload": workload, "blocks_per_gpu": n, "sharding": "contiguous block range per GPU, no collective"},
             "roofline": roofline(w, kern_ms, traffic, traffic_source, bare),
             "per_rank": ranks,
+            "full": args.full,
             "correctness": check_text(flags, n_checked, verified),
         }
         out["config"]["placement"] = placement_text(placed, probe, classes)
@@ -1133,13 +1153,14 @@ def main():
         if cpu is not None:
             out["cpu_baseline"] = cpu
 
-    # ---- second leg: BASELINE.json configs[4] strong-scaled over the same ranks ------------------
+    # ---- second leg: BASELINE.json configs[4] strong-scaled over the same ranks (--full, or only for its --dump-outputs) ----
     bad = not all(flags)
-    if not args.no_config5 and not strong_main:
+    if not args.no_config5 and not strong_main and (args.full or args.dump_outputs):
         c5 = config5_leg(args, world, rank, dev, ctl)
-        bad = bad or not all(c5.pop("flags"))
-        if rank == 0:
-            out["config5_strong"] = c5
+        if c5 is not None:
+            bad = bad or not all(c5.pop("flags"))
+            if rank == 0:
+                out["config5_strong"] = c5
 
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -27,7 +27,7 @@ def _one_json_line(stdout):
 
 @pytest.mark.parametrize("n", [2, 8])
 def test_self_spawn_runs_n_ranks(n):
-    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--backend", "gloo", "--dry-run", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--backend", "gloo", "--dry-run", "--full", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, env=_clean_env())
     assert r.returncode == 0, r.stderr
     out = _one_json_line(r.stdout)
@@ -72,7 +72,7 @@ def test_a_failing_rank_fails_the_launch():
 def test_rccl_failure_falls_back_to_gloo():
     """The data path needs no collective, so RCCL must never be a single point of failure: with no GPU here the RCCL
     probe (a throw-away child per rank) fails, every rank agrees over gloo, and the run completes on gloo saying so."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--probe-nccl", "--nccl-probe-timeout", "30",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--probe-nccl", "--nccl-probe-timeout", "30",
                         "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=300, env=_clean_env())
     assert r.returncode == 0, r.stderr
     out = _one_json_line(r.stdout)
@@ -82,13 +82,20 @@ def test_rccl_failure_falls_back_to_gloo():
 
 
 def test_one_mismatching_rank_fails_every_rank():
-    """per_rank[i].correct is gathered from every rank and any False makes the launch exit non-zero."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--dry-run", "--inject-mismatch", "1",
-                        "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=300, env=_clean_env())
+    """With --full, per_rank[i].correct is gathered from every rank and any False makes the launch exit non-zero.  Without
+    --full a run times the headline only: no verdict is gathered (the injected mismatch has nothing to fail), no config5_strong
+    leg runs, and the line says it was not a --full run."""
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--dry-run", "--inject-mismatch", "1", "--steps", "1", "--warmup", "0"]
+    r = subprocess.run(cmd + ["--full"], capture_output=True, text=True, timeout=300, env=_clean_env())
     assert r.returncode != 0
     out = _one_json_line(r.stdout)
     assert [p["correct"] for p in out["per_rank"]] == [True, False]
     assert "MISMATCH" in out["correctness"] and "1" in out["correctness"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=_clean_env())
+    assert r.returncode == 0, r.stderr
+    out = _one_json_line(r.stdout)
+    assert out["full"] is False and out["config5_strong"] is None and out["correctness"] is None
+    assert out["per_rank"] == [{"rank": 0}, {"rank": 1}] and out["blocks_per_rank"] == [10_000_000] * 2
 
 
 @pytest.mark.parametrize("extra", [["--steps", "0"], ["--warmup", "-1"], ["--dry-run", "--dump-outputs", "dumps"]])

@@ -55,7 +55,7 @@ for stage in "$@"; do
     FL_LIB=$PWD/fastlanes_amd/libfastlanes_amd_full.so timeout 2400 python tools/abchain.py 3 --all --gb 45 --types u32,u64 --only undelta_pack,undelta_pack_2b 2>&1 | grep -v amdgpu > $R/abchain_two_blocks.txt
     grep -c MISMATCH $R/abchain_two_blocks.txt; tail -n 4 $R/abchain_two_blocks.txt ;;
   bench)
-    timeout 900 python bench.py > $R/bench_u32w7.json 2> $R/bench.err; echo "bench rc=$?"; cat $R/bench_u32w7.json ;;
+    timeout 900 python bench.py --full > $R/bench_u32w7.json 2> $R/bench.err; echo "bench rc=$?"; cat $R/bench_u32w7.json ;;
   *) echo "unknown stage $stage" ;;
   esac
 done

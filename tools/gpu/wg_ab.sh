@@ -4,7 +4,7 @@ for wg in ${WGS:-256 128 64}; do   # WGS="256 512": only workloads whose table e
   lib=$PWD/fastlanes_amd/libfastlanes_amd.so; [ $wg != 256 ] && lib=$PWD/fastlanes_amd/libfastlanes_amd_wg$wg.so
   FL_LIB=$lib timeout 300 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -k "device_resident or all_widths_vs_oracle" 2>&1 | tail -1
   for wl in u32_w7_unpack u32_mixed_unpack u64_w17_pack; do
-    FL_LIB=$lib timeout 300 python bench.py --workload $wl --no-cpu-baseline --no-pmc --no-config5 --no-dispatch-check --verify sample > $R/wg${wg}_$wl.json 2> $R/wg${wg}_$wl.err
+    FL_LIB=$lib timeout 300 python bench.py --full --workload $wl --no-cpu-baseline --no-pmc --no-config5 --no-dispatch-check --verify sample > $R/wg${wg}_$wl.json 2> $R/wg${wg}_$wl.err
     python - <<PY
 import json
 try:
