@@ -74,6 +74,20 @@ def _signatures(ty):
     return dev
 
 
+def _for_compare_signatures(ty):
+    """FL_DECLARE_FOR_COMPARE of include/fastlanes_amd.h (device tier): selection masks from FoR-packed columns."""
+    c = CTYPE[ty]
+    return {
+        "unfor_compare": [_U, _P, _P, _Z, ctypes.c_int, c, _Z, _P, _P],
+        "unfor_compare_widths": [_P, _P, _P, _Z, _P, _Z, ctypes.c_int, c, _Z, _P, _P, _P],
+    }
+
+
+def for_compare_symbols():
+    """The symbols FL_DECLARE_FOR_COMPARE declares, all four element types."""
+    return [f"fl_{ty}_{m}" for ty in TYPES for m in _for_compare_signatures(ty)]
+
+
 # include/fastlanes_amd_internal.h: test / measurement hooks, not part of the stable ABI
 INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_policy", "fl_internal_probe_memory_classes",
                     "fl_internal_bare_stream", "fl_internal_bare_stream_shape", "fl_internal_zero_copy_fallbacks",
@@ -82,7 +96,8 @@ INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_pol
 
 
 def exported_symbols():
-    """Every symbol include/fastlanes_amd.h and include/fastlanes_amd_internal.h declare."""
+    """Every symbol include/fastlanes_amd.h and include/fastlanes_amd_internal.h declare, except FL_DECLARE_FOR_COMPARE's
+    (for_compare_symbols)."""
     names = ["fl_version", "fl_status_string", "fl_last_hip_error", "fl_packed_len",
              "fl_mixed_plan_create", "fl_mixed_plan_destroy", "fl_mixed_plan_n_blocks",
              "fl_mixed_plan_packed_bytes", "fl_mixed_plan_offsets", "fl_mixed_plan_widths",
@@ -167,7 +182,7 @@ def load():
     lib.fl_widths_to_offsets.restype = ctypes.c_int
     lib.fl_widths_to_offsets.argtypes = [_U, _P, _Z, _P, _P, _P, _P]
     for ty in TYPES:
-        for m, argtypes in _signatures(ty).items():
+        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty)}.items():
             fn = getattr(lib, f"fl_{ty}_{m}")
             fn.restype = ctypes.c_int
             fn.argtypes = argtypes

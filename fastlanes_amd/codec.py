@@ -383,6 +383,34 @@ class FoR:
         aux, stride, scalar = FoR._ref(src, ty, reference, n)
         return _run("unfor_pack", ty, width, src, out, n, aux=aux, aux_stride=stride, scalar=scalar)
 
+    # ---- extension -----------------------------------------------------------
+    @staticmethod
+    def unfor_compare(width, packed, reference, op, constant, n_blocks=None, output=None):
+        """Selection mask straight from a FoR-packed column: bit i of block b's 1024-bit mask =
+        (FoR.unfor_pack(width, block b, reference)[i] <op> constant), op in '==','!=','<','<=','>','>=' (unsigned,
+        wrapping references allowed).  A block whose reference and width decide the predicate is answered without reading
+        its packed bytes.  A plain bit-packed column is filtered with reference 0.  Device tier only; returns a CUDA int32
+        tensor of 32 words per block (bit i of word i//32, LSB first) -- `output` (32 * n_blocks 4-byte elements) if given.
+        n_blocks is only needed for width == 0."""
+        import torch
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_compare is device tier (pass CUDA tensors)")
+        if width > _lib.BITS[ty]:
+            raise FastLanesError(1, f"fl_{ty}_unfor_compare")
+        n = _blocks(src.n, packed_len(ty, width), "unfor_compare input")
+        if n is None:
+            n = n_blocks if n_blocks is not None else (output.numel() // 32 if output is not None else 0)
+        out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare")
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        k = _lib.CTYPE[ty](int(constant) & ((1 << _lib.BITS[ty]) - 1))
+        with torch.cuda.device(src.x.device):
+            _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare")(width, src.ptr, aux.ptr, stride, BitPacking.CMP[op], k, n,
+                                                                  out.data_ptr(), _stream(src)),
+                   f"fl_{ty}_unfor_compare")
+        return out
+
 
 class Delta:
     """delta.rs:6-17.  `base` holds LANES = 1024/T elements per block."""
@@ -580,6 +608,41 @@ def unfor_pack_widths(widths, offsets, packed, references, output=None, check=Tr
     out = _out(src, output, ty, n * 1024, "unfor_pack_widths")
     _widths_call("unfor_pack_widths", ty, widths, offsets, src, out, check, aux)
     return out.x
+
+
+def unfor_compare_widths(widths, offsets, packed, references, op, constant, output=None, check=True):
+    """FoR.unfor_compare over a mixed-width column: bit i of block b's 1024-bit mask =
+    (FoR::unfor_pack::<widths[b]>(&packed[offsets[b]..], references[b])[i] <op> constant) -- `references` a CUDA tensor of one
+    scalar per block (or a single one, broadcast).  A plain bit-packed mixed-width column is filtered with ONE zero reference
+    (reference_stride 0).  Returns a CUDA int32 tensor of 32 words per block (`output` if given).  The per-block device checks
+    of unfor_pack_widths: a block that fails them is skipped (its 32 mask words are left as they were); `check=True` reads the
+    device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    import torch
+    src = _Arg(packed)
+    ty = src.ty
+    w = _Arg(widths, "u8")
+    o = _Arg(offsets, "u64")
+    _same_tier(src, w, o)
+    if not src.torch:
+        raise TypeError("unfor_compare_widths is device tier: widths, offsets and data must be CUDA tensors")
+    n = w.n
+    if o.n != n:
+        raise ValueError("offsets must hold one entry per block")
+    if op not in BitPacking.CMP:
+        raise ValueError(f"op must be one of {sorted(BitPacking.CMP)}")
+    r, (rptr, stride) = _block_references(src, ty, references, n)
+    out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_widths")
+    dev = src.x.device
+    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
+    k = _lib.CTYPE[ty](int(constant) & ((1 << _lib.BITS[ty]) - 1))
+    with torch.cuda.device(dev):
+        _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare_widths")(w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, BitPacking.CMP[op], k,
+                                                                     n, out.data_ptr(), err.data_ptr() if check else None, _stream(src)),
+               f"fl_{ty}_unfor_compare_widths")
+    if check:
+        _check_flag(err, f"fl_{ty}_unfor_compare_widths")       # bitpacking.rs:93,126 unreachable!(); :111-113
+    return out
 
 
 def for_pack_widths(widths, offsets, input, references, output, check=True):

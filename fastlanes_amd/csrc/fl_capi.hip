@@ -14,6 +14,7 @@
 #include "fl_batch.hpp"
 #include "fl_scan.hpp"
 #include "fl_consume.hpp"
+#include "fl_for_compare.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -577,6 +578,47 @@ int run_chain_widths(int op, const uint8_t* widths, const uint64_t* offsets, con
     return rc >= 0 ? rc : hip_fail(hipErrorInvalidDeviceFunction);
 }
 
+// unfor_compare over a uniform-width column (mixed = false: `width`, blocks back to back) or a mixed-width one (widths[] / offsets[],
+// checked per block by the kernel); fl_for_compare.hpp.  The predicate becomes its cyclic interval here, once per call.
+template <typename T>
+int run_unfor_compare(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
+                      const T* refs, size_t ref_stride, int op, T constant, size_t n_blocks, uint32_t* mask, uint32_t* err_flag,
+                      void* stream)
+{
+    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (op < FL_CMP_EQ || op > FL_CMP_GE) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
+    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
+    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
+    if (!refs || !mask || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask)) return FL_ERR_ALIGN;
+    const ForPredicate p = for_compare_predicate(Elem<T>::BITS, op, constant);
+    ForCompareArgs a;
+    a.packed = reinterpret_cast<const char*>(packed);
+    a.unpacked = nullptr;
+    a.widths = mixed ? widths : nullptr;
+    a.offsets = mixed ? offsets : nullptr;
+    a.err_flag = mixed ? err_flag : nullptr;
+    a.refs = nullptr;                        // the kernel loads cmp_refs with the block's metadata
+    a.ref_stride = ref_stride;
+    a.n_blocks = n_blocks;
+    a.uniform_width = mixed ? 0u : width;
+    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated here, on the host side
+    // the shape of unfor_pack_widths: the same blocks, the same reads, a mask of 1/T of its writes
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
+    a.linear_map = 0;
+    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    a.mask = reinterpret_cast<char*>(mask);
+    a.cmp_refs = refs;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = p.none ? 1u : 0u;
+    return hip_status(for_compare_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
 template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n, uint8_t* widths, void* s)
 {
     if (n == 0) return FL_OK;
@@ -870,6 +912,11 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
     { FL_DEVICE_TIER(s, in, sums); return dev_unpack_block_sums<T>(w, in, n, sums, s); }                                               \
     int fl_##S##_unpack_compare(unsigned w, const T* in, int op, T k, size_t n, uint32_t* mask, void* s)  \
     { FL_DEVICE_TIER(s, in, mask); return dev_unpack_compare<T>(w, in, op, k, n, mask, s); }                                           \
+    int fl_##S##_unfor_compare(unsigned w, const T* in, const T* r, size_t rs, int op, T k, size_t n, uint32_t* mask, void* s) \
+    { FL_DEVICE_TIER(s, in, r, mask); return run_unfor_compare<T>(false, w, nullptr, nullptr, in, 0, r, rs, op, k, n, mask, nullptr, s); } \
+    int fl_##S##_unfor_compare_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, int op, T k, \
+                                      size_t n, uint32_t* mask, uint32_t* ef, void* s)                   \
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, ef); return run_unfor_compare<T>(true, 0, w, o, pk, pb, r, rs, op, k, n, mask, ef, s); }     \
     int fl_##S##_block_min_max(const T* in, size_t n, T* mins, T* maxs, void* s)                          \
     { FL_DEVICE_TIER(s, in, mins, maxs); return dev_block_min_max<T>(in, n, mins, maxs, s); }                                                \
     int fl_##S##_transpose(const T* in, T* out, size_t n, void* s) { FL_DEVICE_TIER(s, in, out); return dev_transpose<T>(false, in, out, n, s); } \

@@ -6,12 +6,14 @@
 //   6 wave-per-block kernels: unpack / pack over per-block (or uniform) widths (fl_widths.hpp), Delta chains (fl_chain.hpp)
 //   10 fused consumers: unpack_block_sums, block_min_max   11 / 12 unpack_compare (selection masks: x <= k / x == k)
 //   8 undelta_pack+untranspose (fused decode to original order)   9 transpose+delta+pack (fused encode)
+//   13 unfor_compare (selection masks from FoR-packed columns, uniform or mixed width; fl_for_compare.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
 #include "fl_chain.hpp"
 #include "fl_batch.hpp"
 #include "fl_consume.hpp"
+#include "fl_for_compare.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -116,7 +118,9 @@ template <> const CompareTable<T>& compare_table_impl<T, false>() { return t_com
 #elif FL_FAMILY == 12
 static constexpr CompareTable<T> t_compare_eq = make_compare_table<T, true>(Ws{});
 template <> const CompareTable<T>& compare_table_impl<T, true>() { return t_compare_eq; }
+#elif FL_FAMILY == 13
+template <> for_compare_launch_t for_compare_launcher<T>() { return &launch_unfor_compare<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..12"
+#error "FL_FAMILY must be 0..6 or 8..13"
 #endif
 }  // namespace fl

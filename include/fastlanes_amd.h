@@ -375,6 +375,31 @@ FL_DECLARE_TYPE(uint16_t, u16)
 FL_DECLARE_TYPE(uint32_t, u32)
 FL_DECLARE_TYPE(uint64_t, u64)
 
+/*
+ * EXTENSION: selection masks from FoR-packed columns, defined as the composition
+ *     bit i of mask[b*32 .. b*32+32) = (unfor_pack::<W_b>(block b, references[b*reference_stride])[i] <op> constant)
+ * (ffor.rs:38-50, wrapping_add; i in the unpacked index order, LSB first: the layout of fl_<ty>_unpack_compare; op an fl_cmp,
+ * unsigned, any other value FL_ERR_INDEX; reference_stride 0 broadcasts references[0]).  W_b is `width` in the uniform form (`in`
+ * holds n_blocks blocks of 128*width bytes, back to back) and widths[b] at offsets[b] in the mixed-width form, which runs the
+ * per-block device checks of fl_<ty>_unfor_pack_widths: a failing block is skipped -- its 32 mask words are left untouched -- and its
+ * FL_DEVERR_* bit is ORed into *err_flag.  A block's reference r and width W bound its values to the cyclic range [r, r + 2^W - 1]:
+ * a block that range decides (every value satisfies the predicate, or none does) is answered from its metadata alone and its packed
+ * bytes are never read.  A plain bit-packed column is filtered with one zero reference and reference_stride 0.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list above is a pinned surface.)
+ */
+#define FL_DECLARE_FOR_COMPARE(T, S)                                                                      \
+    int fl_##S##_unfor_compare(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                               int op, T constant, size_t n_blocks, uint32_t *mask, void *stream);       \
+    int fl_##S##_unfor_compare_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,   \
+                                      size_t packed_bytes, const T *references, size_t reference_stride, \
+                                      int op, T constant, size_t n_blocks, uint32_t *mask,               \
+                                      uint32_t *err_flag, void *stream);
+
+FL_DECLARE_FOR_COMPARE(uint8_t, u8)
+FL_DECLARE_FOR_COMPARE(uint16_t, u16)
+FL_DECLARE_FOR_COMPARE(uint32_t, u32)
+FL_DECLARE_FOR_COMPARE(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

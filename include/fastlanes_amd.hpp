@@ -59,6 +59,8 @@ template <typename T> struct Abi;
         static constexpr auto unpack_block_sums = fl_##S##_unpack_block_sums;                        \
         static constexpr auto block_min_max = fl_##S##_block_min_max;                                \
         static constexpr auto unpack_compare = fl_##S##_unpack_compare;                              \
+        static constexpr auto unfor_compare = fl_##S##_unfor_compare;                                \
+        static constexpr auto unfor_compare_widths = fl_##S##_unfor_compare_widths;                  \
         static constexpr auto unpack_mixed = fl_##S##_unpack_mixed;                                  \
         static constexpr auto pack_mixed = fl_##S##_pack_mixed;                                      \
         static constexpr auto unpack_widths = fl_##S##_unpack_widths;                                \
@@ -185,6 +187,10 @@ template <typename T> struct FoR : BitPacking<T> {
     static void unfor_pack_device(std::size_t width, const T* d_in, const T* d_refs, std::size_t ref_stride, T* d_out,
                                   std::size_t n_blocks, void* stream = nullptr)
     { detail::check(A::unfor_pack((unsigned)width, d_in, d_refs, ref_stride, d_out, n_blocks, stream), "unfor_pack_device"); }
+    // mask bit i of block b = (unfor_pack(block b, d_refs[b * ref_stride])[i] <op> constant); 32 words per block
+    static void unfor_compare_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, fl_cmp op, T constant,
+                                     std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
+    { detail::check(A::unfor_compare((unsigned)width, d_packed, d_refs, ref_stride, (int)op, constant, n_blocks, d_mask, stream), "unfor_compare_device"); }
 };
 
 // delta.rs:6-17
@@ -402,6 +408,12 @@ inline void unfor_pack_widths_device(const std::uint8_t* d_widths, const std::ui
                                      const T* d_references, std::size_t reference_stride, T* d_out, std::size_t n_blocks,
                                      std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_pack_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_out, n_blocks, d_err_flag, stream), "unfor_pack_widths"); }
+// the selection mask of the same column: bit i of block b = (unfor_pack::<widths[b]>(..)[i] <op> constant), 32 words per block
+template <typename T>
+inline void unfor_compare_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                        const T* d_references, std::size_t reference_stride, fl_cmp op, T constant, std::size_t n_blocks,
+                                        std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_compare_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, (int)op, constant, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_widths"); }
 template <typename T>
 inline void for_pack_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_in, const T* d_references,
                                    std::size_t reference_stride, T* d_packed, std::size_t packed_bytes, std::size_t n_blocks,

@@ -6,7 +6,10 @@ the 8 TB/s HBM peak, G ints/s."""
 import argparse
 import json
 import os
+import re
 import sys
+
+import numpy as np
 
 import torch
 
@@ -251,6 +254,7 @@ def main():
                          "class of memory, the other side arranged for the eight XCDs' write positions")
     ap.add_argument("--window-ab", action="store_true", help="every row also under the whole-column tile map and under 2^16-block windows")
     ap.add_argument("--bare", action="store_true", help="pack / unpack / FoR / undelta_pack rows: also a bare stream of the row's bytes on the row's buffers (always on for allwidths)")
+    ap.add_argument("--rows", default="", help="--cases mixed: keep only the rows whose name matches this regular expression")
     ap.add_argument("--batch-all", action="store_true", help="--cases batch: every element type and the pack direction too")
     ap.add_argument("--batch-policies", default="", help="--cases batch: comma-separated kernel policies to time next to the default")
     args = ap.parse_args()
@@ -527,8 +531,39 @@ def main():
         # FoR's and Delta's bodies over device-resident mixed-width columns (fl_<ty>_unfor_pack_widths, ..) next to plain
         # unpack_widths / pack_widths of the same column, and an encoder's whole chain: block_min_max -> for_widths ->
         # widths_to_offsets -> for_pack_widths (two passes over the values).  Widths seeded-random in 1..T-1, separate tensors.
+        # unfor_compare_widths rows (selection masks from the FoR-packed column; bytes per block 1 + 8 + sizeof(T) + 128 of metadata and
+        # mask, plus the 128 * W packed bytes of every UNDECIDED block): an undecided predicate (every block's value range straddles
+        # the constant), and `x < k` at the 1 % quantile of an ascending column encoded by the library's own chain -- mostly decided from
+        # the blocks' metadata -- with unfor_pack_widths of that column as its yardstick.  Each row prints its decided share.
         lib = fl.load()
+        keep = re.compile(args.rows) if args.rows else None
+        NPDT = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "u64": np.uint64}
+        SIGNED = {"u8": torch.uint8, "u16": torch.int16, "u32": torch.int32, "u64": torch.int64}     # int64 -> T by truncation
+
+        def time_row(name, nbytes, f, tail=""):
+            if keep and not keep.search(name):
+                return
+            f(); f()
+            torch.cuda.synchronize()
+            if not nbytes:
+                return
+            ms = []
+            for _ in range(args.reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); f(); b.record(); b.synchronize()
+                ms.append(a.elapsed_time(b))
+            med = sorted(ms)[len(ms) // 2]
+            print(f"{name:32s} {ty:4s} n={n:>9d} {med:9.4f} ms {nbytes / med / 1e6:8.1f} GB/s {nbytes / med / 8e9:.3f} "
+                  f"{n * 1024 / med / 1e6:8.1f} Gint/s{tail}", flush=True)
+
+        def lt_decided(T, w_host, r_host, k):
+            """the blocks `x < k` decides from (reference, width) alone -- fl_for_decide.hpp's rule with a = 0, s = k - 1, c = r"""
+            r = r_host.astype(object)
+            return np.array([int(x) + (1 << int(w)) - 1 <= k - 1 or int(x) >= k for x, w in zip(r, w_host)], dtype=bool)
+
         for ty in ("u32", "u64", "u16", "u8"):
+            if args.types and ty not in args.types.split(","):
+                continue
             T, esz = ESZ[ty] * 8, ESZ[ty]
             L = 1024 // T
             n = max(64, int(args.gb * 1e9 / (128 * T * 1.5)))
@@ -582,19 +617,44 @@ def main():
                 ("FoR encoder chain (4 launches)", 2 * n * 128 * T + pbytes, encoder_chain),
             )
             for name, nbytes, f in rows:
-                f(); f()
-                torch.cuda.synchronize()
-                if not nbytes:
-                    continue
-                ms = []
-                for _ in range(args.reps):
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record(); f(); b.record(); b.synchronize()
-                    ms.append(a.elapsed_time(b))
-                med = sorted(ms)[len(ms) // 2]
-                print(f"{name:32s} {ty:4s} n={n:>9d} {med:9.4f} ms {nbytes / med / 1e6:8.1f} GB/s {nbytes / med / 8e9:.3f} "
-                      f"{n * 1024 / med / 1e6:8.1f} Gint/s", flush=True)
-            del col, un, back, refs, bases, mm, un_enc, bases_enc
+                time_row(name, nbytes, f)
+            meta = 1 + 8 + esz + 128
+            w_host = widths.cpu().numpy()
+            mask = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            if not keep or keep.search("unfor_compare_widths undecided"):
+                # references k - 1 - (x mod (2^W - 1)): every block's range [r, r + 2^W - 1] holds k - 1 and k, so `x < k` decides none
+                k = 1 << (T - 1)
+                x = np.random.default_rng(5).integers(0, 1 << 62, size=n, dtype=np.uint64)
+                und = np.array([(k - 1 - int(v) % ((1 << int(w)) - 1)) % (1 << T) for v, w in zip(x, w_host)], dtype=np.uint64)
+                refs_und = torch.from_numpy(und.astype(NPDT[ty])).to(dev)
+                dec = lt_decided(T, w_host, und, k)
+                nbytes = n * meta + int((128 * w_host.astype(np.int64))[~dec].sum())
+                time_row("unfor_compare_widths undecided", nbytes,
+                         lambda: fl.unfor_compare_widths(widths, offsets, col, refs_und, "<", k, output=mask, check=False),
+                         f"  decided {dec.mean():.3f}")
+            if not keep or keep.search("unfor_pack_widths ascending") or keep.search("unfor_compare_widths ascending <1%"):
+                # an ascending column through the library's own encoder chain
+                i = torch.arange(n * 1024, dtype=torch.int64, device=dev)
+                asc = i * ((1 << T) - 1) // (n * 1024) if T <= 32 else i * 3          # the type's whole range (u64: a slope of 3)
+                k1 = int(asc[len(asc) // 100].item())
+                asc_v = asc.to(SIGNED[ty]).view(TDT[ty])
+                del asc, i
+                lo, hi = fl.BitPacking.block_min_max(asc_v)
+                w_asc = fl.for_widths(lo, hi)
+                o_asc, t_asc = fl.widths_to_offsets(ty, w_asc)
+                pk_asc = torch.empty(max(int(t_asc.item()) // esz, 1), dtype=TDT[ty], device=dev)
+                fl.for_pack_widths(w_asc, o_asc, asc_v, lo, pk_asc, check=False)
+                del asc_v
+                wa, la = w_asc.cpu().numpy(), lo.view(torch.uint8).cpu().numpy().view(NPDT[ty])
+                dec = lt_decided(T, wa, la, k1)
+                pb = int(t_asc.item())
+                time_row("unfor_pack_widths ascending", pb + n * 128 * T, lambda: fl.unfor_pack_widths(w_asc, o_asc, pk_asc, lo, output=un, check=False))
+                nbytes = n * meta + int((128 * wa.astype(np.int64))[~dec].sum())
+                time_row("unfor_compare_widths ascending <1%", nbytes,
+                         lambda: fl.unfor_compare_widths(w_asc, o_asc, pk_asc, lo, "<", k1, output=mask, check=False),
+                         f"  decided {dec.mean():.3f}")
+                del pk_asc, lo, hi, w_asc, o_asc
+            del col, un, back, refs, bases, mm, un_enc, bases_enc, mask
             if pair is not None:
                 pair.free()
                 pair_enc.free()
