@@ -22,7 +22,7 @@ struct BatchArgs {
     const void* refs;            // FoR: references[a], one per ARRAY (ffor.rs:24-50); nullptr = plain BitPacking
     uint64_t n_arrays;
     uint64_t tiles_per_xcd = 0;
-    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile)
+    unsigned window_shift = 63;  // tile-map window (fl_tile_map.hpp: xcd_tile)
     unsigned tiles_per_array;    // ceil(max_blocks / (4 * bpw))
     unsigned max_blocks;         // the caller's bound on n_blocks[a]
     unsigned bpw;                // consecutive blocks of the array per wavefront (>= 1); a workgroup takes 4 * bpw

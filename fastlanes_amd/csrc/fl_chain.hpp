@@ -45,7 +45,7 @@ struct ChainArgs {
     const char* bases;       // [n_blocks][128 bytes]; unused by CHAIN_NONE
     uint64_t n_blocks;
     uint64_t tiles_per_xcd = 0;
-    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); both filled by the launcher
+    unsigned window_shift = 63;  // tile-map window (fl_tile_map.hpp: xcd_tile); both filled by the launcher
     unsigned width;          // SRC_PACKED / SNK_PACKED only
     // mixed-width form of the packed side (SRC_PACKED / SNK_PACKED only; fl_widths.hpp's surface): block b has widths[b] and its
     // 128*widths[b] bytes start at byte offsets[b] of the packed column.  nullptr = every block has `width`, back to back.

@@ -30,7 +30,7 @@ struct ReduceArgs {
     void* out1;            // maxs (T per block) or unused
     uint64_t n_blocks;
     uint64_t tiles_per_xcd = 0;
-    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); both filled by the launcher
+    unsigned window_shift = 63;  // tile-map window (fl_tile_map.hpp: xcd_tile); both filled by the launcher
 };
 
 __device__ __forceinline__ bool tile_of_workgroup(const ReduceArgs& a, uint64_t& tile)
@@ -184,7 +184,7 @@ struct CompareArgs {
     uint32_t invert;       // complement the result
     uint64_t n_blocks;
     uint64_t tiles_per_xcd = 0;
-    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); both filled by the launcher
+    unsigned window_shift = 63;  // tile-map window (fl_tile_map.hpp: xcd_tile); both filled by the launcher
 };
 
 // u8 / u16 compare SWAR-wise: all elements of a 32-bit word at once, the verdict of an element landing in ONE bit of its

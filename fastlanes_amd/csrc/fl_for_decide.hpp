@@ -11,10 +11,12 @@
 #pragma once
 #include <stdint.h>
 
+#ifndef FL_HD            // (also defined, identically, by fl_tile_map.hpp)
 #if defined(__HIPCC__) || defined(__HIP__)
 #define FL_HD __host__ __device__
 #else
 #define FL_HD
+#endif
 #endif
 
 namespace fl {

@@ -43,7 +43,7 @@ struct WidthsArgs {
     uint64_t packed_bytes;     // size of the packed column: a block must lie inside [0, packed_bytes) (only read when widths != nullptr)
     unsigned prefetch;         // bpw > 1: 1 = request all bpw blocks of the wavefront up front by LDS-DMA (one LDS image per block)
     unsigned linear_map;       // A/B tools: 1 = workgroup b takes tile b instead of the XCD-contiguous map
-    unsigned window_shift = 63;  // tile-map window (fl_kernels.hpp: xcd_tile); filled by the launcher
+    unsigned window_shift = 63;  // tile-map window (fl_tile_map.hpp: xcd_tile); filled by the launcher
     unsigned nt_from;          // RD_AUTO: uniform widths >= this stream non-temporally by LDS-DMA (fl_dispatch.hpp: nt_read_from)
 };
 

@@ -9,7 +9,7 @@ opposite (6.8 / 6.35); a thin write stream next to a bulk read stream of the sam
 kernel moves by a few per cent with the allocation its buffers happen to lie in -- and nothing in an address tells.
 
 What the repository does with that since round 4:
-  * the KERNELS use the read / write asymmetry themselves (the tile-map window, fl_kernels.hpp: xcd_tile);
+  * the KERNELS use the read / write asymmetry themselves (the tile-map window, fl_tile_map.hpp: xcd_tile);
   * bench.py --placement auto treats the layout as a measurement: it allocates both layouts it knows -- one allocation per buffer,
     and `column_pair` below -- times a few launches on each BEFORE its timed region and keeps the faster buffers.  Round 3 shipped
     `column_pair` as the default and it cost one workload 9 %;

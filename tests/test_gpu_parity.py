@@ -1055,7 +1055,7 @@ def test_functor_api_user_kernel_on_iterate_rows(fl, oracle):
 
 @pytest.mark.parametrize("ty", TYS)
 def test_results_do_not_depend_on_the_tile_map(fl, oracle, ty):
-    """fl_kernels.hpp: xcd_tile -- which workgroup takes which tile is chosen for speed (round 4: read-dominated kernels walk the
+    """fl_tile_map.hpp: xcd_tile -- which workgroup takes which tile is chosen for speed (round 4: read-dominated kernels walk the
     column in windows) and must never change a byte.  Every family under windows of 2^8, 2^9 and 2^12 blocks (many windows, a
     short last one: the block count is ragged against all of them) and under the whole-column map, with both kernel designs,
     against the default's output -- which the other tests tie to the oracle -- and, for unpack, against the oracle directly."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the tile-map window (fl_kernels.hpp: xcd_tile) for every kernel family, same buffers, launches interleaved round-robin.
+"""A/B of the tile-map window (fl_tile_map.hpp: xcd_tile) for every kernel family, same buffers, launches interleaved round-robin.
     python tools/abwindow.py [--reps 9] [--gb 48] [--windows 31,12,14,16,18,20] [--cases matrix] [--ops pack,delta] [--constructed]
 Window = log2 of the window in 1024-value blocks (fastlanes_amd_internal.h: policy bits 25-29); 31 = one window = the whole-column
 map of rounds 1-3; 0 = the library's own choice per kernel.  Prints GB/s of algorithmic bytes per (op, window)."""

@@ -182,7 +182,7 @@ def run(op, ty, w, gb, reps):
     gbps = n * bpb / med / 1e6
     if WINDOW_AB:
         # the same buffers under the whole-column tile map of rounds 1-3 (window 31) and under 2^16-block windows, whatever the
-        # library's own choice for this kernel is (fl_kernels.hpp: xcd_tile), round-robin
+        # library's own choice for this kernel is (fl_tile_map.hpp: xcd_tile), round-robin
         big = {"u64": 20, "u32": 21, "u16": 22, "u8": 23}[ty]            # 8 GiB of unpacked blocks per window
         alt = {31: [], 16: [], big: []}
         for _ in range(reps):
