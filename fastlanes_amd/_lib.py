@@ -88,6 +88,20 @@ def for_compare_symbols():
     return [f"fl_{ty}_{m}" for ty in TYPES for m in _for_compare_signatures(ty)]
 
 
+def _select_signatures(ty):
+    """FL_DECLARE_SELECT of include/fastlanes_amd.h (device tier): only the rows a selection mask keeps, from FoR-packed columns."""
+    return {
+        "unfor_select": [_U, _P, _P, _Z, _P, _P, _P, _Z, _Z, _P, _P],
+        "unfor_select_widths": [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _Z, _P, _P],
+    }
+
+
+def select_symbols():
+    """The symbols FL_DECLARE_MASK_OFFSETS and FL_DECLARE_SELECT declare: the mask prefix sum and, for all four element types, the
+    two select entry points."""
+    return ["fl_mask_offsets"] + [f"fl_{ty}_{m}" for ty in TYPES for m in _select_signatures(ty)]
+
+
 # include/fastlanes_amd_internal.h: test / measurement hooks, not part of the stable ABI
 INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_policy", "fl_internal_probe_memory_classes",
                     "fl_internal_bare_stream", "fl_internal_bare_stream_shape", "fl_internal_zero_copy_fallbacks",
@@ -97,7 +111,7 @@ INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_pol
 
 def exported_symbols():
     """Every symbol include/fastlanes_amd.h and include/fastlanes_amd_internal.h declare, except FL_DECLARE_FOR_COMPARE's
-    (for_compare_symbols)."""
+    (for_compare_symbols) and FL_DECLARE_MASK_OFFSETS' / FL_DECLARE_SELECT's (select_symbols)."""
     names = ["fl_version", "fl_status_string", "fl_last_hip_error", "fl_packed_len",
              "fl_mixed_plan_create", "fl_mixed_plan_destroy", "fl_mixed_plan_n_blocks",
              "fl_mixed_plan_packed_bytes", "fl_mixed_plan_offsets", "fl_mixed_plan_widths",
@@ -181,8 +195,10 @@ def load():
     lib.fl_internal_column_pair_classes.argtypes = [_P]
     lib.fl_widths_to_offsets.restype = ctypes.c_int
     lib.fl_widths_to_offsets.argtypes = [_U, _P, _Z, _P, _P, _P, _P]
+    lib.fl_mask_offsets.restype = ctypes.c_int
+    lib.fl_mask_offsets.argtypes = [_P, _Z, _P, _P, _P]
     for ty in TYPES:
-        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty)}.items():
+        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty), **_select_signatures(ty)}.items():
             fn = getattr(lib, f"fl_{ty}_{m}")
             fn.restype = ctypes.c_int
             fn.argtypes = argtypes

@@ -411,6 +411,29 @@ class FoR:
                    f"fl_{ty}_unfor_compare")
         return out
 
+    @staticmethod
+    def unfor_select(width, packed, reference, mask, out_offsets=None, total=None, n_blocks=None, output=None, check=True):
+        """Only the rows a selection mask keeps: the values FoR.unfor_pack(width, packed, reference) yields where `mask` (the layout
+        unfor_compare returns: a CUDA int32 tensor of 32 words per block, bit i of word i//32, LSB first) has a 1, compacted, in
+        column order.  A block whose mask is empty is never read.  A plain bit-packed column is selected with reference 0.  Device
+        tier only.  `out_offsets` / `total` are mask_offsets(mask)'s results (computed here if not given); with `output=None` the
+        total is read back once to size the result (one sync), otherwise `output` receives the values and only its first `total`
+        elements are written.  `check=True` reads the device error flag back (one sync) and raises if a block's run did not fit
+        `output` (such a block is skipped either way); `check=False` stays asynchronous.  n_blocks is only needed for width == 0."""
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_select is device tier (pass CUDA tensors)")
+        if width > _lib.BITS[ty]:
+            raise FastLanesError(1, f"fl_{ty}_unfor_select")
+        n = _blocks(src.n, packed_len(ty, width), "unfor_select input")
+        if n is None:
+            n = n_blocks if n_blocks is not None else (mask.numel() // 32 if _is_torch(mask) else 0)
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        return _select_call(f"fl_{ty}_unfor_select", ty, src, n, mask, out_offsets, total, output, check,
+                            lambda tail: (width, src.ptr, aux.ptr, stride, *tail))
+
+
 
 class Delta:
     """delta.rs:6-17.  `base` holds LANES = 1024/T elements per block."""
@@ -643,6 +666,90 @@ def unfor_compare_widths(widths, offsets, packed, references, op, constant, outp
     if check:
         _check_flag(err, f"fl_{ty}_unfor_compare_widths")       # bitpacking.rs:93,126 unreachable!(); :111-113
     return out
+
+
+def _select_mask(src, mask, n):
+    """The selection mask of a select call: a CUDA tensor of 32 four-byte integer words per block, on the column's device."""
+    m = _Arg(mask)
+    _same_tier(src, m)
+    if m.x.dtype.is_floating_point or m.x.element_size() != 4:
+        raise TypeError(f"mask must be an int32 / uint32 tensor (32 words per block), got {m.x.dtype}")
+    if m.n != 32 * n:
+        raise ValueError(f"mask holds {m.n} words, expected 32 per block = {32 * n}")
+    return m
+
+
+def mask_offsets(mask):
+    """Device tier: (out_offsets, total) for a selection mask (a CUDA int32 / uint32 tensor of 32 words per block, as the compare
+    functions return) -- out_offsets[b] = number of mask bits set in the blocks before b = where block b's kept values start in
+    the compacted output of unfor_select (a CUDA int64 tensor, in elements), total = a 1-element CUDA int64 tensor holding the
+    number of kept values.  No host round trip."""
+    import torch
+    if not _is_torch(mask):
+        raise TypeError("mask_offsets is device tier (pass a CUDA int32 tensor)")
+    m = _Arg(mask)
+    if m.x.dtype.is_floating_point or m.x.element_size() != 4:
+        raise TypeError(f"mask must be an int32 / uint32 tensor (32 words per block), got {m.x.dtype}")
+    if m.n % 32:
+        raise ValueError(f"mask holds {m.n} words, not a multiple of 32 (one block)")
+    dev = m.x.device
+    n = m.n // 32
+    offsets = torch.empty(n, dtype=torch.int64, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(_lib.load().fl_mask_offsets(m.ptr, n, offsets.data_ptr(), total.data_ptr(), _stream(m)), "fl_mask_offsets")
+    return offsets, total
+
+
+def _select_call(name, ty, src, n, mask, out_offsets, total, output, check, args):
+    """The part the two select forms share: mask / out_offsets / output validation, the launch, the error flag.  `args(tail)`
+    puts the form's own leading C arguments in front of (mask, out_offsets, out, out_len, n_blocks, err_flag, stream)."""
+    import torch
+    m = _select_mask(src, mask, n)
+    if out_offsets is None:
+        out_offsets, total = mask_offsets(m.x)
+    oo = _Arg(out_offsets, "u64")
+    _same_tier(src, oo)
+    if oo.n != n:
+        raise ValueError("out_offsets must hold one entry per block")
+    dev = src.x.device
+    if output is None:
+        if total is None:
+            raise ValueError("output=None needs `total` (mask_offsets' second result) to size the result")
+        out = _Arg(torch.empty(int(total.item()), dtype=src.x.dtype, device=dev), ty)       # the one sync
+    else:
+        out = _Arg(output, ty)
+        _same_tier(src, out)
+    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+    with torch.cuda.device(dev):
+        _check(getattr(_lib.load(), name)(*args((m.ptr, oo.ptr, out.ptr, out.n, n, err.data_ptr() if check else None, _stream(src)))), name)
+    if check:
+        _check_flag(err, name)              # a run outside `output`; the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113
+    return out.x
+
+
+def unfor_select_widths(widths, offsets, packed, references, mask, out_offsets=None, total=None, output=None, check=True):
+    """FoR.unfor_select over a mixed-width column: the values unfor_pack_widths(widths, offsets, packed, references) yields where
+    `mask` (32 words per block, unfor_compare_widths' layout) has a 1, compacted, in column order -- `references` a CUDA tensor of
+    one scalar per block (or a single one, broadcast; ONE zero reference selects from a plain bit-packed column).  A block whose
+    mask is empty is never read.  `out_offsets` / `total` are mask_offsets(mask)'s results (computed here if not given); with
+    `output=None` the total is read back once to size the result (one sync).  The per-block device checks of unfor_pack_widths: a
+    block that fails them, or whose run does not fit `output`, is skipped (its output slots are left as they were); `check=True`
+    reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    src = _Arg(packed)
+    ty = src.ty
+    w = _Arg(widths, "u8")
+    o = _Arg(offsets, "u64")
+    _same_tier(src, w, o)
+    if not src.torch:
+        raise TypeError("unfor_select_widths is device tier: widths, offsets and data must be CUDA tensors")
+    n = w.n
+    if o.n != n:
+        raise ValueError("offsets must hold one entry per block")
+    r, (rptr, stride) = _block_references(src, ty, references, n)
+    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
+    return _select_call(f"fl_{ty}_unfor_select_widths", ty, src, n, mask, out_offsets, total, output, check,
+                        lambda tail: (w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, *tail))
 
 
 def for_pack_widths(widths, offsets, input, references, output, check=True):

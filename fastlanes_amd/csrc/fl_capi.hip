@@ -15,6 +15,7 @@
 #include "fl_scan.hpp"
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
+#include "fl_select.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -619,6 +620,47 @@ int run_unfor_compare(bool mixed, unsigned width, const uint8_t* widths, const u
     return hip_status(for_compare_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
+// unfor_select over a uniform-width column (mixed = false) or a mixed-width one (widths[] / offsets[], checked per block by the kernel);
+// fl_select.hpp.  Launched with the shape of unfor_pack_widths, as unfor_compare is.
+template <typename T>
+int run_unfor_select(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
+                     const T* refs, size_t ref_stride, const uint32_t* mask, const uint64_t* out_offsets, T* out, size_t out_len,
+                     size_t n_blocks, uint32_t* err_flag, void* stream)
+{
+    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (n_blocks == 0) return FL_OK;
+    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
+    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
+    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
+    // a selection that keeps nothing has no output: `out` may be NULL with out_len == 0 (a non-empty block then fails the kernel's
+    // bounds check; nothing is ever written through this pointer)
+    if (!out && out_len == 0) out = const_cast<T*>(no_bytes);
+    if (!refs || !mask || !out_offsets || !out || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask) || misaligned(out)) return FL_ERR_ALIGN;
+    SelectArgs a;
+    a.packed = reinterpret_cast<const char*>(packed);
+    a.unpacked = nullptr;
+    a.widths = mixed ? widths : nullptr;
+    a.offsets = mixed ? offsets : nullptr;
+    a.err_flag = err_flag;                   // the uniform form raises FL_DEVERR_BOUNDS too (a run outside `out`)
+    a.refs = nullptr;                        // the kernel loads sel_refs with the block's metadata
+    a.ref_stride = ref_stride;
+    a.n_blocks = n_blocks;
+    a.uniform_width = mixed ? 0u : width;
+    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated here, on the host side
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
+    a.linear_map = 0;
+    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    a.mask = mask;
+    a.out_offsets = out_offsets;
+    a.out = reinterpret_cast<char*>(out);
+    a.out_len = out_len;
+    a.sel_refs = refs;
+    return hip_status(select_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
 template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n, uint8_t* widths, void* s)
 {
     if (n == 0) return FL_OK;
@@ -702,6 +744,14 @@ int fl_widths_to_offsets(unsigned type_bits, const uint8_t* widths, size_t n_blo
     FL_DEVICE_TIER(stream, widths, offsets, total_bytes, err_flag);
     ScanArgs a{widths, offsets, total_bytes, err_flag, n_blocks, type_bits};
     return hip_status(launch_widths_to_offsets(a, static_cast<hipStream_t>(stream)));
+}
+
+int fl_mask_offsets(const uint32_t* mask, size_t n_blocks, uint64_t* out_offsets, uint64_t* total, void* stream)
+{
+    if (n_blocks && (!mask || !out_offsets)) return FL_ERR_NULL;
+    if (n_blocks && misaligned(mask)) return FL_ERR_ALIGN;
+    FL_DEVICE_TIER(stream, mask, out_offsets, total);
+    return hip_status(launch_mask_offsets(mask, n_blocks, out_offsets, total, static_cast<hipStream_t>(stream)));
 }
 
 int fl_mixed_plan_create(unsigned type_bits, const uint8_t* widths, size_t n_blocks, fl_mixed_plan** plan)
@@ -1017,6 +1067,19 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
         return host_run<T>(in, n * 1024, nullptr, 0, out, n * 1024,                                       \
                            [&](const T* di, const T*, T* d_o, void* st) { return dev_transpose<T>(true, di, d_o, n, st); }); \
     }
+
+#define FL_DEFINE_SELECT(T, S)                                                                            \
+    int fl_##S##_unfor_select(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, const uint64_t* oo, T* out, size_t ol, \
+                              size_t n, uint32_t* ef, void* s)                                            \
+    { FL_DEVICE_TIER(s, in, r, mask, oo, out, ef); return run_unfor_select<T>(false, w, nullptr, nullptr, in, 0, r, rs, mask, oo, out, ol, n, ef, s); } \
+    int fl_##S##_unfor_select_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
+                                     const uint64_t* oo, T* out, size_t ol, size_t n, uint32_t* ef, void* s) \
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, oo, out, ef); return run_unfor_select<T>(true, 0, w, o, pk, pb, r, rs, mask, oo, out, ol, n, ef, s); }
+
+FL_DEFINE_SELECT(uint8_t, u8)
+FL_DEFINE_SELECT(uint16_t, u16)
+FL_DEFINE_SELECT(uint32_t, u32)
+FL_DEFINE_SELECT(uint64_t, u64)
 
 FL_DEFINE_TYPE(uint8_t, u8)
 FL_DEFINE_TYPE(uint16_t, u16)

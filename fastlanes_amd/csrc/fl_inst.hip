@@ -7,6 +7,7 @@
 //   10 fused consumers: unpack_block_sums, block_min_max   11 / 12 unpack_compare (selection masks: x <= k / x == k)
 //   8 undelta_pack+untranspose (fused decode to original order)   9 transpose+delta+pack (fused encode)
 //   13 unfor_compare (selection masks from FoR-packed columns, uniform or mixed width; fl_for_compare.hpp)
+//   14 unfor_select (only the rows a selection mask keeps, from the same columns; fl_select.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -14,6 +15,7 @@
 #include "fl_batch.hpp"
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
+#include "fl_select.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -120,7 +122,9 @@ static constexpr CompareTable<T> t_compare_eq = make_compare_table<T, true>(Ws{}
 template <> const CompareTable<T>& compare_table_impl<T, true>() { return t_compare_eq; }
 #elif FL_FAMILY == 13
 template <> for_compare_launch_t for_compare_launcher<T>() { return &launch_unfor_compare<T>; }
+#elif FL_FAMILY == 14
+template <> select_launch_t select_launcher<T>() { return &launch_unfor_select<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..13"
+#error "FL_FAMILY must be 0..6 or 8..14"
 #endif
 }  // namespace fl

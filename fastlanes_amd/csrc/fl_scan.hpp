@@ -116,6 +116,60 @@ inline hipError_t launch_widths_to_offsets(const ScanArgs& a, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------
+// selection mask -> out_offsets (fl_select.hpp): the exclusive prefix sum of the blocks' popcounts, in ELEMENTS -- where block b's kept
+// values start in the compacted output of unfor_select -- and the number of kept values.  The same three launches; only the first
+// differs: a chunk's 4096 masks (128 bytes per block) are read fully coalesced, 16 bytes per thread per step (the 8 threads of a block's
+// mask add up their popcounts), the per-block counts pass through LDS to the thread that owns 16 consecutive blocks, and from there on
+// it is k_scan_local.  k_scan_chunks / k_scan_add run unchanged (they only see offsets[] and *total).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void k_mask_scan_local(const u32x4* mask, ScanArgs a)
+{
+    __shared__ uint16_t kept[SCAN_CHUNK];                      // a block keeps at most 1024 values
+    const uint64_t chunk0 = (uint64_t)blockIdx.x * SCAN_CHUNK;
+    const uint64_t left = a.n_blocks - chunk0;
+    const unsigned pieces = (unsigned)(left < (uint64_t)SCAN_CHUNK ? left : (uint64_t)SCAN_CHUNK) * 8u;   // 16-byte pieces of this chunk's masks
+    const u32x4* src = mask + chunk0 * 8u;
+    for (unsigned p = threadIdx.x; p < SCAN_CHUNK * 8u; p += WG) {      // the same trip count for every thread
+        unsigned c = 0;
+        if (p < pieces) {
+            const u32x4 v = __builtin_nontemporal_load(src + p);
+            c = __builtin_popcount(v.x) + __builtin_popcount(v.y) + __builtin_popcount(v.z) + __builtin_popcount(v.w);
+        }
+        c += __shfl_xor(c, 1, 64);
+        c += __shfl_xor(c, 2, 64);
+        c += __shfl_xor(c, 4, 64);
+        if ((p & 7u) == 0u) kept[p >> 3] = (uint16_t)c;
+    }
+    __syncthreads();
+    const unsigned b0 = threadIdx.x * SCAN_PER_THREAD;
+    const uint64_t t0 = chunk0 + b0;
+    uint64_t sum = 0;
+    for (int e = 0; e < SCAN_PER_THREAD; ++e) sum += kept[b0 + e];     // blocks past the column hold 0
+    uint64_t total;
+    uint64_t run = wg_excl_scan(sum, &total);
+    for (int e = 0; e < SCAN_PER_THREAD; ++e) {
+        if (t0 + e < a.n_blocks) a.offsets[t0 + e] = (threadIdx.x == 0 && e == 0) ? total : run;
+        run += kept[b0 + e];
+    }
+}
+
+inline hipError_t launch_mask_offsets(const uint32_t* mask, uint64_t n_blocks, uint64_t* out_offsets, uint64_t* total, hipStream_t s)
+{
+    if (n_blocks == 0) {
+        if (total) return hipMemsetAsync(total, 0, sizeof(uint64_t), s);
+        return hipSuccess;
+    }
+    const ScanArgs a{nullptr, out_offsets, total, nullptr, n_blocks, 0};
+    const unsigned n_chunks = (unsigned)((n_blocks + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    FL_LAUNCH(k_mask_scan_local, dim3(n_chunks), dim3(WG), 0, s, reinterpret_cast<const u32x4*>(mask), a);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    FL_LAUNCH(k_scan_chunks, dim3(1), dim3(WG), 0, s, a);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    FL_LAUNCH(k_scan_add, dim3(n_chunks), dim3(WG), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // An encoder's width choice for FoR with reference = the block's minimum (ffor.rs:24-36 packs `in[idx] - reference`, masked to
 // W bits by macros.rs:73): widths[b] = number of bits of maxs[b] - mins[b] (0 when the block is constant) is the smallest W that
 // loses nothing.  The reference has no width selection (closing note); this is the arithmetic its callers do

@@ -400,6 +400,43 @@ FL_DECLARE_FOR_COMPARE(uint16_t, u16)
 FL_DECLARE_FOR_COMPARE(uint32_t, u32)
 FL_DECLARE_FOR_COMPARE(uint64_t, u64)
 
+/*
+ * EXTENSION (SURVEY.md 8(f2) "unpack -> filter", 8(f4) "take"): decode only the rows a selection mask keeps.  For a FoR-packed
+ * column, uniform or mixed width, and a mask in the layout the compare entry points write (32 uint32 words per block, bit i of
+ * block b = bit i % 32 of word b*32 + i/32, i in the unpacked index order):
+ *     out = concat over b ascending of [ unfor_pack::<W_b>(block b, references[b*reference_stride])[i]  for i ascending if bit i ]
+ * (ffor.rs:38-50) -- the kept values, compacted, in column order.  A plain bit-packed column is selected with one zero reference and
+ * reference_stride 0.  Delta columns are out of scope: a selected value needs its whole chain.  Two steps, both asynchronous on
+ * `stream`, no allocation, no synchronisation:
+ *   1. the mask-offsets call (type-independent): out_offsets[b] = number of mask bits set in blocks 0..b-1 (a device uint64 array, in
+ *      ELEMENTS), *total (device uint64, may be NULL) = the number of kept values.  Three small launches, no scratch memory.
+ *   2. fl_<ty>_unfor_select / fl_<ty>_unfor_select_widths: block b's kept values go to out[out_offsets[b] ..].  The count is taken from
+ *      the block's own mask bits; a block whose run does not lie inside [0, out_len) is SKIPPED and FL_DEVERR_BOUNDS is ORed into
+ *      *err_flag, so a wrong out_offsets array never writes outside `out`.  The mixed-width form runs the per-block device checks of
+ *      fl_<ty>_unfor_pack_widths: a failing block is skipped, its output slots are left untouched, its FL_DEVERR_* bit is raised.
+ *      A block whose mask is all zero is never read: no packed load, no store.
+ * `out`, `mask` and the packed column are 16-byte aligned (FL_ERR_ALIGN); a block's own destination is only element-aligned.
+ * A selection that keeps nothing has no output: `out` may be NULL when out_len is 0.
+ * (Declared by macros of their own: FL_DECLARE_TYPE's per-type list and the list of other functions are pinned surfaces.)
+ */
+#define FL_DECLARE_MASK_OFFSETS(NAME)                                                                     \
+    int fl_##NAME(const uint32_t *mask, size_t n_blocks, uint64_t *out_offsets, uint64_t *total, void *stream);
+FL_DECLARE_MASK_OFFSETS(mask_offsets)
+
+#define FL_DECLARE_SELECT(T, S)                                                                           \
+    int fl_##S##_unfor_select(unsigned width, const T *in, const T *references, size_t reference_stride,  \
+                              const uint32_t *mask, const uint64_t *out_offsets, T *out, size_t out_len,  \
+                              size_t n_blocks, uint32_t *err_flag, void *stream);                         \
+    int fl_##S##_unfor_select_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,     \
+                                     size_t packed_bytes, const T *references, size_t reference_stride,   \
+                                     const uint32_t *mask, const uint64_t *out_offsets, T *out,           \
+                                     size_t out_len, size_t n_blocks, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_SELECT(uint8_t, u8)
+FL_DECLARE_SELECT(uint16_t, u16)
+FL_DECLARE_SELECT(uint32_t, u32)
+FL_DECLARE_SELECT(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,8 @@ template <typename T> struct Abi;
         static constexpr auto unpack_compare = fl_##S##_unpack_compare;                              \
         static constexpr auto unfor_compare = fl_##S##_unfor_compare;                                \
         static constexpr auto unfor_compare_widths = fl_##S##_unfor_compare_widths;                  \
+        static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
+        static constexpr auto unfor_select_widths = fl_##S##_unfor_select_widths;                    \
         static constexpr auto unpack_mixed = fl_##S##_unpack_mixed;                                  \
         static constexpr auto pack_mixed = fl_##S##_pack_mixed;                                      \
         static constexpr auto unpack_widths = fl_##S##_unpack_widths;                                \
@@ -191,6 +193,11 @@ template <typename T> struct FoR : BitPacking<T> {
     static void unfor_compare_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, fl_cmp op, T constant,
                                      std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
     { detail::check(A::unfor_compare((unsigned)width, d_packed, d_refs, ref_stride, (int)op, constant, n_blocks, d_mask, stream), "unfor_compare_device"); }
+    // only the values of unfor_pack(..) whose mask bit is set, compacted: block b's go to d_out[d_out_offsets[b] ..] (mask_offsets_device)
+    static void unfor_select_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
+                                    const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
+                                    std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_select((unsigned)width, d_packed, d_refs, ref_stride, d_mask, d_out_offsets, d_out, out_len, n_blocks, d_err_flag, stream), "unfor_select_device"); }
 };
 
 // delta.rs:6-17
@@ -414,6 +421,17 @@ inline void unfor_compare_widths_device(const std::uint8_t* d_widths, const std:
                                         const T* d_references, std::size_t reference_stride, fl_cmp op, T constant, std::size_t n_blocks,
                                         std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_compare_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, (int)op, constant, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_widths"); }
+// selection mask -> where each block's kept values start in the compacted output (elements), and how many there are in all
+inline void mask_offsets_device(const std::uint32_t* d_mask, std::size_t n_blocks, std::uint64_t* d_out_offsets, std::uint64_t* d_total = nullptr,
+                                void* stream = nullptr)
+{ detail::check(fl_mask_offsets(d_mask, n_blocks, d_out_offsets, d_total, stream), "mask_offsets"); }
+// ... and the kept values themselves: unfor_pack_widths_device's output where the mask has a 1, compacted, in column order
+template <typename T>
+inline void unfor_select_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                       const T* d_references, std::size_t reference_stride, const std::uint32_t* d_mask,
+                                       const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
+                                       std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_select_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, d_out_offsets, d_out, out_len, n_blocks, d_err_flag, stream), "unfor_select_widths"); }
 template <typename T>
 inline void for_pack_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_in, const T* d_references,
                                    std::size_t reference_stride, T* d_packed, std::size_t packed_bytes, std::size_t n_blocks,

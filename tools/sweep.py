@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput sweep over the kernel families (HIP-event timing, random data, HBM-resident).
-    python tools/sweep.py [--gb 24] [--reps 7] [--cases all|quick]
+    python tools/sweep.py [--gb 24] [--reps 7] [--cases all|quick|mixed|select|...]
 Prints one line per (op, type, width): ms, GB/s (algorithmic bytes), fraction of
 the 8 TB/s HBM peak, G ints/s."""
 import argparse
@@ -658,6 +658,101 @@ def main():
             if pair is not None:
                 pair.free()
                 pair_enc.free()
+            torch.cuda.empty_cache()
+        return
+    if args.cases == "select":
+        # unfor_select_widths (decode only the rows a selection mask keeps) over the mixed-width column of --cases mixed, at random mask
+        # densities 0 .. 100 % and one clustered mask (one block in 16 non-empty, 50 % inside it).  Two yardsticks, unchanged kernels, are
+        # timed in the SAME run on the SAME buffers, round-robin with the row under test: unfor_pack_widths of the column (the select's
+        # output lies at the start of its output buffer) and unfor_compare_widths with every block decided (`x < 0`: metadata-only traffic,
+        # a 128-byte mask written per block where select reads one).  Algorithmic bytes per block: packed bytes of the NON-EMPTY blocks
+        # + 128 (mask) + 8 (out_offsets) + kept * sizeof(T).  mask_offsets (three launches) is timed on a line of its own.
+        lib = fl.load()
+        reps = max(args.reps, 5)
+
+        def round_robin(variants):
+            """{name: [ms, ...]}: `reps` timed launches of every variant, interleaved, after two untimed rounds"""
+            for _ in range(2):
+                for f in variants.values():
+                    f()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in variants}
+            for _ in range(reps):
+                for k, f in variants.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); f(); b.record(); b.synchronize()
+                    ms[k].append(a.elapsed_time(b))
+            return ms
+
+        def random_mask(n, density, seed, every=1):
+            """int32 words of a random mask, built 32 Ki blocks at a time; every > 1: only blocks b % every == 0 keep anything"""
+            g = torch.Generator(device=dev); g.manual_seed(seed)
+            out = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            sh = torch.arange(32, device=dev)
+            for b0 in range(0, n, 32768):
+                nb = min(32768, n - b0)
+                if density <= 0.0 or density >= 1.0:
+                    bits = torch.full((nb * 1024,), density >= 1.0, dtype=torch.bool, device=dev)
+                else:
+                    bits = torch.rand(nb * 1024, device=dev, generator=g) < density
+                if every > 1:
+                    bits &= ((torch.arange(b0, b0 + nb, device=dev) % every) == 0).repeat_interleave(1024)
+                w64 = (bits.view(-1, 32).to(torch.int64) << sh).sum(dim=1)
+                out[b0 * 32:(b0 + nb) * 32] = torch.where(w64 >= 1 << 31, w64 - (1 << 32), w64).to(torch.int32)
+            return out
+
+        for ty in ("u32", "u64", "u16", "u8"):
+            if args.types and ty not in args.types.split(","):
+                continue
+            T, esz = ESZ[ty] * 8, ESZ[ty]
+            n = max(64, int(args.gb * 1e9 / (128 * T * 1.5)))
+            g = torch.Generator(device=dev); g.manual_seed(31 + T)
+            widths = torch.randint(1, T, (n,), dtype=torch.int64, device=dev, generator=g).to(torch.uint8)
+            offsets, total = fl.widths_to_offsets(ty, widths)
+            pbytes = int(total.item())
+            pair = None
+            if PLACEMENT == "interleaved":
+                from fastlanes_amd import placement as pl
+                pair = pl.ColumnPair(pbytes, n * 128 * T, dev, aux_bytes=n * 128, layout="interleaved")
+                print(f"# {ty}: constructed pair, measured classes (input first): {pair.classes}", flush=True)
+                col, un = pair.input.view(TDT[ty]), pair.output.view(TDT[ty])
+                col.view(torch.uint8).copy_(rnd(pbytes, 1))
+            else:
+                col = rnd(pbytes, 1).view(TDT[ty])
+                un = torch.empty(n * 1024, dtype=TDT[ty], device=dev)
+            refs = rnd(n * 8, 2).view(torch.uint8).view(-1, 8)[:, :esz].contiguous().view(TDT[ty]).reshape(-1)
+            cmp_mask = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            w_host = widths.cpu().numpy().astype(np.int64)
+            two_sided = pbytes + n * 128 * T
+            print(f"# {ty}: n = {n} blocks, packed {pbytes / 1e9:.2f} GB, unpacked {n * 128 * T / 1e9:.2f} GB, {reps} launches each, round-robin", flush=True)
+            rows = [("0", 0.0, 1), ("1/1024", 1 / 1024, 1), ("1 %", 0.01, 1), ("10 %", 0.1, 1), ("50 %", 0.5, 1), ("100 %", 1.0, 1), ("clustered 1/16 x 50 %", 0.5, 16)]
+            for name, density, every in rows:
+                mask = random_mask(n, density, 77 + T, every)
+                oo, tot = fl.mask_offsets(mask)
+                kept = int(tot.item())
+                starts = oo.cpu().numpy()
+                pop = np.diff(np.concatenate([starts, [kept]]))
+                nbytes = int((128 * w_host)[pop > 0].sum()) + n * (128 + 8) + kept * esz
+                ms = round_robin({
+                    "select": lambda: fl.unfor_select_widths(widths, offsets, col, refs, mask, out_offsets=oo, total=tot, output=un, check=False),
+                    "unfor_pack_widths": lambda: fl.unfor_pack_widths(widths, offsets, col, refs, output=un, check=False),
+                    "compare all decided": lambda: fl.unfor_compare_widths(widths, offsets, col, refs, "<", 0, output=cmp_mask, check=False),
+                    "mask_offsets": lambda: fl.mask_offsets(mask),
+                })
+                med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+                sel = med["select"]
+                print(f"unfor_select_widths {name:22s} {ty:4s} kept {kept / (n * 1024):7.4f} non-empty {float((pop > 0).mean()):6.4f}  {sel:9.4f} ms (min {min(ms['select']):9.4f})  "
+                      f"{nbytes / sel / 1e6:8.1f} GB/s {nbytes / sel / 8e9:.3f}  {nbytes / n:7.0f} B/block  "
+                      f"x{sel / med['unfor_pack_widths']:.3f} of unfor_pack_widths ({med['unfor_pack_widths']:.4f} ms, {two_sided / med['unfor_pack_widths'] / 8e9:.3f})  "
+                      f"x{sel / med['compare all decided']:.3f} of compare all decided ({med['compare all decided']:.4f} ms)", flush=True)
+                print(f"    mask_offsets {ty:4s} {med['mask_offsets']:9.4f} ms (min {min(ms['mask_offsets']):.4f})  {n * 136 / med['mask_offsets'] / 1e6:8.1f} GB/s", flush=True)
+                if density == 0.0:
+                    for k in ("select", "compare all decided"):
+                        print(f"    spread at density 0: {k:20s} min {min(ms[k]):.4f} median {med[k]:.4f} max {max(ms[k]):.4f} ms", flush=True)
+                del mask, oo, tot
+            del col, un, refs, cmp_mask
+            if pair is not None:
+                pair.free()
             torch.cuda.empty_cache()
         return
     if args.cases == "single":
