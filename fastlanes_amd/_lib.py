@@ -102,6 +102,20 @@ def select_symbols():
     return ["fl_mask_offsets"] + [f"fl_{ty}_{m}" for ty in TYPES for m in _select_signatures(ty)]
 
 
+def _aggregate_signatures(ty):
+    """FL_DECLARE_AGGREGATE of include/fastlanes_amd.h (device tier): count / sum / min / max per block of the rows a mask keeps."""
+    return {
+        "unfor_aggregate": [_U, _P, _P, _Z, _P, _Z, _P, _P, _P],
+        "unfor_aggregate_widths": [_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P],
+    }
+
+
+def aggregate_symbols():
+    """The symbols FL_DECLARE_AGGREGATE and FL_DECLARE_AGGREGATE_REDUCE declare: for all four element types the two aggregate entry
+    points, and the reduction of their per-block slots."""
+    return [f"fl_{ty}_{m}" for ty in TYPES for m in _aggregate_signatures(ty)] + ["fl_aggregate_reduce"]
+
+
 # include/fastlanes_amd_internal.h: test / measurement hooks, not part of the stable ABI
 INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_policy", "fl_internal_probe_memory_classes",
                     "fl_internal_bare_stream", "fl_internal_bare_stream_shape", "fl_internal_zero_copy_fallbacks",
@@ -111,7 +125,8 @@ INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_pol
 
 def exported_symbols():
     """Every symbol include/fastlanes_amd.h and include/fastlanes_amd_internal.h declare, except FL_DECLARE_FOR_COMPARE's
-    (for_compare_symbols) and FL_DECLARE_MASK_OFFSETS' / FL_DECLARE_SELECT's (select_symbols)."""
+    (for_compare_symbols), FL_DECLARE_MASK_OFFSETS' / FL_DECLARE_SELECT's (select_symbols) and FL_DECLARE_AGGREGATE's /
+    FL_DECLARE_AGGREGATE_REDUCE's (aggregate_symbols)."""
     names = ["fl_version", "fl_status_string", "fl_last_hip_error", "fl_packed_len",
              "fl_mixed_plan_create", "fl_mixed_plan_destroy", "fl_mixed_plan_n_blocks",
              "fl_mixed_plan_packed_bytes", "fl_mixed_plan_offsets", "fl_mixed_plan_widths",
@@ -197,8 +212,10 @@ def load():
     lib.fl_widths_to_offsets.argtypes = [_U, _P, _Z, _P, _P, _P, _P]
     lib.fl_mask_offsets.restype = ctypes.c_int
     lib.fl_mask_offsets.argtypes = [_P, _Z, _P, _P, _P]
+    lib.fl_aggregate_reduce.restype = ctypes.c_int
+    lib.fl_aggregate_reduce.argtypes = [_P, _Z, _P, _P]
     for ty in TYPES:
-        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty), **_select_signatures(ty)}.items():
+        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty), **_select_signatures(ty), **_aggregate_signatures(ty)}.items():
             fn = getattr(lib, f"fl_{ty}_{m}")
             fn.restype = ctypes.c_int
             fn.argtypes = argtypes

@@ -433,6 +433,28 @@ class FoR:
         return _select_call(f"fl_{ty}_unfor_select", ty, src, n, mask, out_offsets, total, output, check,
                             lambda tail: (width, src.ptr, aux.ptr, stride, *tail))
 
+    @staticmethod
+    def unfor_aggregate(width, packed, reference, mask=None, n_blocks=None, block_aggs=None, check=True):
+        """COUNT / SUM / MIN / MAX of the values FoR.unfor_pack(width, packed, reference) yields where `mask` (the layout unfor_compare
+        returns: a CUDA int32 tensor of 32 words per block) has a 1 -- `mask=None`: of every value, and no mask is read -- without
+        materialising them.  Returns (result, block_aggs): `block_aggs` a CUDA int64[n_blocks, 4] tensor of the blocks' own
+        aggregates (`block_aggs` if given), `result` a CUDA int64[4] tensor of their combination; both hold uint64 bit patterns in
+        the order count, sum (wrapping mod 2^64), min, max; nothing kept gives (0, 0, 2^64 - 1, 0).  A block whose mask is empty, or
+        whose width is 0, is never read.  A plain bit-packed column is aggregated with reference 0.  Device tier only; no host round
+        trip (`check` only matters for the mixed-width form).  n_blocks is only needed for width == 0 without a mask."""
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_aggregate is device tier (pass CUDA tensors)")
+        if width > _lib.BITS[ty]:
+            raise FastLanesError(1, f"fl_{ty}_unfor_aggregate")
+        n = _blocks(src.n, packed_len(ty, width), "unfor_aggregate input")
+        if n is None:
+            n = n_blocks if n_blocks is not None else (mask.numel() // 32 if _is_torch(mask) else 0)
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        return _aggregate_call(f"fl_{ty}_unfor_aggregate", src, n, mask, block_aggs, check,
+                               lambda tail: (width, src.ptr, aux.ptr, stride, *tail))
+
 
 
 class Delta:
@@ -750,6 +772,68 @@ def unfor_select_widths(widths, offsets, packed, references, mask, out_offsets=N
     pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
     return _select_call(f"fl_{ty}_unfor_select_widths", ty, src, n, mask, out_offsets, total, output, check,
                         lambda tail: (w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, *tail))
+
+
+def aggregate_reduce(block_aggs):
+    """Device tier: the combination of per-block aggregates (a CUDA int64 tensor of 4 words per block, as unfor_aggregate returns) --
+    counts and sums added (wrapping), the smallest min, the largest max -- as a CUDA int64[4] tensor: count, sum, min, max (uint64 bit
+    patterns).  No blocks give the identity (0, 0, 2^64 - 1, 0).  Deterministic; no host round trip."""
+    import torch
+    if not _is_torch(block_aggs):
+        raise TypeError("aggregate_reduce is device tier (pass a CUDA int64 tensor)")
+    g = _Arg(block_aggs)
+    if g.x.dtype.is_floating_point or g.x.element_size() != 8:
+        raise TypeError(f"block_aggs must be an int64 / uint64 tensor (4 words per block), got {g.x.dtype}")
+    if g.n % 4:
+        raise ValueError(f"block_aggs holds {g.n} words, not a multiple of 4 (one block)")
+    dev = g.x.device
+    result = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(_lib.load().fl_aggregate_reduce(g.ptr if g.n else None, g.n // 4, result.data_ptr(), _stream(g)), "fl_aggregate_reduce")
+    return result
+
+
+def _aggregate_call(name, src, n, mask, block_aggs, check, args):
+    """The part the two aggregate forms share: mask / block_aggs validation, the two launches, the error flag.  `args(tail)` puts the
+    form's own leading C arguments in front of (mask, n_blocks, block_aggs, err_flag, stream)."""
+    import torch
+    m = _select_mask(src, mask, n) if mask is not None else None
+    dev = src.x.device
+    if block_aggs is None:
+        slots = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    else:
+        slots = _consumer_out(src, block_aggs, torch.int64, n * 4, name[name.index("unfor"):]).view(n, 4)
+    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+    with torch.cuda.device(dev):
+        _check(getattr(_lib.load(), name)(*args((m.ptr if m is not None and n else None, n, slots.data_ptr() if n else None,
+                                                 err.data_ptr() if check else None, _stream(src)))), name)
+    result = aggregate_reduce(slots)
+    if check:
+        _check_flag(err, name)              # the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113
+    return result, slots
+
+
+def unfor_aggregate_widths(widths, offsets, packed, references, mask=None, block_aggs=None, check=True):
+    """FoR.unfor_aggregate over a mixed-width column: COUNT / SUM / MIN / MAX of the values unfor_pack_widths(widths, offsets, packed,
+    references) yields where `mask` (32 words per block, unfor_compare_widths' layout; None: everywhere) has a 1 -- `references` a CUDA
+    tensor of one scalar per block (or a single one, broadcast; ONE zero reference aggregates a plain bit-packed column).  Returns
+    (result, block_aggs) as FoR.unfor_aggregate does.  The per-block device checks of unfor_pack_widths: a block that fails them is
+    skipped and ITS SLOT HOLDS THE IDENTITY (0, 0, 2^64 - 1, 0), so `result` combines the valid blocks; `check=True` reads the device
+    error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    src = _Arg(packed)
+    ty = src.ty
+    w = _Arg(widths, "u8")
+    o = _Arg(offsets, "u64")
+    _same_tier(src, w, o)
+    if not src.torch:
+        raise TypeError("unfor_aggregate_widths is device tier: widths, offsets and data must be CUDA tensors")
+    n = w.n
+    if o.n != n:
+        raise ValueError("offsets must hold one entry per block")
+    r, (rptr, stride) = _block_references(src, ty, references, n)
+    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
+    return _aggregate_call(f"fl_{ty}_unfor_aggregate_widths", src, n, mask, block_aggs, check,
+                           lambda tail: (w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, *tail))
 
 
 def for_pack_widths(widths, offsets, input, references, output, check=True):

@@ -16,6 +16,7 @@
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
 #include "fl_select.hpp"
+#include "fl_aggregate.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -661,6 +662,43 @@ int run_unfor_select(bool mixed, unsigned width, const uint8_t* widths, const ui
     return hip_status(select_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
+// unfor_aggregate over a uniform-width column (mixed = false) or a mixed-width one (widths[] / offsets[], checked per block by the kernel:
+// a failing block's slot receives the identity); fl_aggregate.hpp.  Launched with the shape of unfor_pack_widths, as unfor_select is.
+// `mask` may be NULL: every row is kept and no mask is read.
+template <typename T>
+int run_unfor_aggregate(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
+                        const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, void* block_aggs, uint32_t* err_flag,
+                        void* stream)
+{
+    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (n_blocks == 0) return FL_OK;
+    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
+    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
+    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
+    if (!refs || !block_aggs || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask) || misaligned(block_aggs)) return FL_ERR_ALIGN;
+    AggregateArgs a;
+    a.packed = reinterpret_cast<const char*>(packed);
+    a.unpacked = nullptr;
+    a.widths = mixed ? widths : nullptr;
+    a.offsets = mixed ? offsets : nullptr;
+    a.err_flag = mixed ? err_flag : nullptr; // a uniform-width call is validated here, on the host side
+    a.refs = nullptr;                        // the kernel loads agg_refs with the block's metadata
+    a.ref_stride = ref_stride;
+    a.n_blocks = n_blocks;
+    a.uniform_width = mixed ? 0u : width;
+    a.packed_bytes = mixed ? packed_bytes : 0;
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
+    a.linear_map = 0;
+    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    a.mask = mask;
+    a.aggs = static_cast<char*>(block_aggs);
+    a.agg_refs = refs;
+    return hip_status(aggregate_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
 template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n, uint8_t* widths, void* s)
 {
     if (n == 0) return FL_OK;
@@ -752,6 +790,15 @@ int fl_mask_offsets(const uint32_t* mask, size_t n_blocks, uint64_t* out_offsets
     if (n_blocks && misaligned(mask)) return FL_ERR_ALIGN;
     FL_DEVICE_TIER(stream, mask, out_offsets, total);
     return hip_status(launch_mask_offsets(mask, n_blocks, out_offsets, total, static_cast<hipStream_t>(stream)));
+}
+
+int fl_aggregate_reduce(const void* block_aggs, size_t n_blocks, void* result, void* stream)
+{
+    if (!result || (n_blocks && !block_aggs)) return FL_ERR_NULL;
+    if ((n_blocks && misaligned(block_aggs)) || misaligned(result)) return FL_ERR_ALIGN;
+    FL_DEVICE_TIER(stream, block_aggs, result);
+    return hip_status(launch_aggregate_reduce(static_cast<const BlockAggregate*>(block_aggs), n_blocks, static_cast<BlockAggregate*>(result),
+                                              static_cast<hipStream_t>(stream)));
 }
 
 int fl_mixed_plan_create(unsigned type_bits, const uint8_t* widths, size_t n_blocks, fl_mixed_plan** plan)
@@ -1080,6 +1127,19 @@ FL_DEFINE_SELECT(uint8_t, u8)
 FL_DEFINE_SELECT(uint16_t, u16)
 FL_DEFINE_SELECT(uint32_t, u32)
 FL_DEFINE_SELECT(uint64_t, u64)
+
+#define FL_DEFINE_AGGREGATE(T, S)                                                                         \
+    int fl_##S##_unfor_aggregate(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, \
+                                 void* s)                                                                 \
+    { FL_DEVICE_TIER(s, in, r, mask, aggs, ef); return run_unfor_aggregate<T>(false, w, nullptr, nullptr, in, 0, r, rs, mask, n, aggs, ef, s); } \
+    int fl_##S##_unfor_aggregate_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
+                                        size_t n, void* aggs, uint32_t* ef, void* s)                      \
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, aggs, ef); return run_unfor_aggregate<T>(true, 0, w, o, pk, pb, r, rs, mask, n, aggs, ef, s); }
+
+FL_DEFINE_AGGREGATE(uint8_t, u8)
+FL_DEFINE_AGGREGATE(uint16_t, u16)
+FL_DEFINE_AGGREGATE(uint32_t, u32)
+FL_DEFINE_AGGREGATE(uint64_t, u64)
 
 FL_DEFINE_TYPE(uint8_t, u8)
 FL_DEFINE_TYPE(uint16_t, u16)

@@ -8,6 +8,7 @@
 //   8 undelta_pack+untranspose (fused decode to original order)   9 transpose+delta+pack (fused encode)
 //   13 unfor_compare (selection masks from FoR-packed columns, uniform or mixed width; fl_for_compare.hpp)
 //   14 unfor_select (only the rows a selection mask keeps, from the same columns; fl_select.hpp)
+//   15 unfor_aggregate (count / sum / min / max per block of the rows a mask keeps, from the same columns; fl_aggregate.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -16,6 +17,7 @@
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
 #include "fl_select.hpp"
+#include "fl_aggregate.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -124,7 +126,9 @@ template <> const CompareTable<T>& compare_table_impl<T, true>() { return t_comp
 template <> for_compare_launch_t for_compare_launcher<T>() { return &launch_unfor_compare<T>; }
 #elif FL_FAMILY == 14
 template <> select_launch_t select_launcher<T>() { return &launch_unfor_select<T>; }
+#elif FL_FAMILY == 15
+template <> aggregate_launch_t aggregate_launcher<T>() { return &launch_unfor_aggregate<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..14"
+#error "FL_FAMILY must be 0..6 or 8..15"
 #endif
 }  // namespace fl

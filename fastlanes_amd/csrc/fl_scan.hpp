@@ -3,6 +3,7 @@
 // Included by exactly one translation unit of the library (fl_capi.hip), which instantiates what it uses.
 #pragma once
 #include "fl_kernels.hpp"
+#include "fl_aggregate_map.hpp"
 
 namespace fl {
 
@@ -166,6 +167,66 @@ inline hipError_t launch_mask_offsets(const uint32_t* mask, uint64_t n_blocks, u
     FL_LAUNCH(k_scan_chunks, dim3(1), dim3(WG), 0, s, a);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     FL_LAUNCH(k_scan_add, dim3(n_chunks), dim3(WG), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// per-block aggregates -> the column's (fl_aggregate.hpp writes the slots; fl_aggregate_map.hpp: combine / identity).  Integer add, min
+// and max are associative and commutative, so the result does not depend on the order the chunks arrive in.  One workgroup reduces a
+// chunk's 4096 slots (32 bytes each), read fully coalesced, 16 bytes per thread per step: a slot's two halves -- {count, sum} and
+// {min, max} -- fall to an even and an odd thread, and as the step (WG) is even a thread only ever sees one kind.  The chunk's result is
+// folded into *result with four 64-bit vector atomics (relaxed, agent scope); a one-thread launch of the identity precedes it on the same
+// stream.  No scratch memory.
+// ---------------------------------------------------------------------------
+static_assert(WG % 2 == 0, "a thread of k_aggregate_reduce keeps to one half of the slots");
+
+__global__ __launch_bounds__(WG) void k_aggregate_init(BlockAggregate* result)
+{
+    if (threadIdx.x == 0) *result = aggregate_identity();
+}
+
+__global__ __launch_bounds__(WG) void k_aggregate_reduce(const u32x4* slots, uint64_t n_blocks, BlockAggregate* result)
+{
+    __shared__ uint64_t part[WG / 64][4];
+    const uint64_t chunk0 = (uint64_t)blockIdx.x * SCAN_CHUNK;
+    const uint64_t left = n_blocks - chunk0;
+    const unsigned pieces = (unsigned)(left < (uint64_t)SCAN_CHUNK ? left : (uint64_t)SCAN_CHUNK) * 2u;   // 16-byte pieces of this chunk's slots
+    const u32x4* src = slots + chunk0 * 2u;
+    const bool upper = (threadIdx.x & 1u) != 0u;               // false: x = count, y = sum;  true: x = min, y = max
+    uint64_t x = upper ? ~0ull : 0ull, y = 0ull;
+    for (unsigned p = threadIdx.x; p < pieces; p += WG) {
+        const u32x4 v = __builtin_nontemporal_load(src + p);
+        const uint64_t a = ((uint64_t)v.y << 32) | v.x, b = ((uint64_t)v.w << 32) | v.z;
+        x = upper ? (a < x ? a : x) : x + a;
+        y = upper ? (b > y ? b : y) : y + b;
+    }
+    for (int d = 2; d < 64; d <<= 1) {                         // lanes of the same parity
+        const uint64_t a = __shfl_xor(x, d, 64), b = __shfl_xor(y, d, 64);
+        x = upper ? (a < x ? a : x) : x + a;
+        y = upper ? (b > y ? b : y) : y + b;
+    }
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane < 2u) {
+        part[wave][2u * lane] = x;
+        part[wave][2u * lane + 1u] = y;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        BlockAggregate g = aggregate_identity();
+        for (unsigned k = 0; k < WG / 64; ++k) g = aggregate_combine(g, BlockAggregate{part[k][0], part[k][1], part[k][2], part[k][3]});
+        __hip_atomic_fetch_add(&result->count, g.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&result->sum, g.sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_min(&result->min, g.min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&result->max, g.max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+inline hipError_t launch_aggregate_reduce(const BlockAggregate* slots, uint64_t n_blocks, BlockAggregate* result, hipStream_t s)
+{
+    FL_LAUNCH(k_aggregate_init, dim3(1), dim3(WG), 0, s, result);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess || n_blocks == 0) return e;
+    const unsigned n_chunks = (unsigned)((n_blocks + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    FL_LAUNCH(k_aggregate_reduce, dim3(n_chunks), dim3(WG), 0, s, reinterpret_cast<const u32x4*>(slots), n_blocks, result);
     return hipGetLastError();
 }
 

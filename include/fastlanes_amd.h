@@ -437,6 +437,54 @@ FL_DECLARE_SELECT(uint16_t, u16)
 FL_DECLARE_SELECT(uint32_t, u32)
 FL_DECLARE_SELECT(uint64_t, u64)
 
+/*
+ * EXTENSION (SURVEY.md 8(f2) "unpack -> filter" followed by a reduction): COUNT / SUM / MIN / MAX of a FoR-packed column, uniform or
+ * mixed width, over the rows a selection mask keeps -- SELECT COUNT(*), SUM(y), MIN(y), MAX(y) WHERE <mask> -- without materialising
+ * the kept rows.  With the mask in the layout the compare entry points write (32 uint32 words per block, bit i of block b = bit i % 32
+ * of word b*32 + i/32, i in the unpacked index order):
+ *     V_b   = [ unfor_pack::<W_b>(block b, references[b*reference_stride])[i]  for i if bit i of block b ]            (ffor.rs:38-50)
+ *     agg_b = { count = |V_b|,  sum = the sum of V_b (values zero-extended to uint64, wrapping mod 2^64, as unpack_block_sums),
+ *               min = min V_b,  max = max V_b   (unsigned, zero-extended to uint64) }
+ * An empty V_b gives the IDENTITY {0, 0, UINT64_MAX, 0} of
+ *     combine(a, b) = { a.count + b.count, a.sum + b.sum (wrapping), min(a.min, b.min), max(a.max, b.max) }.
+ * mask == NULL keeps every row, and no mask is read.  reference_stride 0 broadcasts references[0]; one zero reference with stride 0
+ * aggregates a plain bit-packed column.  Delta columns are out of scope, as for select.  Two steps, both asynchronous on `stream`, no
+ * allocation, no synchronisation:
+ *   1. fl_<ty>_unfor_aggregate / fl_<ty>_unfor_aggregate_widths: block_aggs[b] = agg_b for EVERY block (a device array of n_blocks
+ *      fl_block_aggregate, 32 bytes each) -- a result in its own right: per-chunk aggregates, zone maps.  A block whose mask is empty,
+ *      or whose width is 0 (every value is its reference), is answered from its metadata: its packed bytes are never read.  The
+ *      mixed-width form runs the per-block device checks of fl_<ty>_unfor_pack_widths: a failing block raises its FL_DEVERR_* bit in
+ *      *err_flag and ITS SLOT RECEIVES THE IDENTITY.  This departs, on purpose, from the "left untouched" of the other mixed-width
+ *      entry points: the slot feeds a reduction, and a skipped block must not inject stale memory into it.
+ *   2. the aggregate-reduce call (type-independent): *result (a device fl_block_aggregate) = combine over block_aggs[0 .. n_blocks);
+ *      n_blocks == 0 gives the identity.  Integer add, min and max are associative and commutative: the result is deterministic.
+ *      Two small launches, no scratch memory.
+ * width > T is FL_ERR_WIDTH (also for an empty column); `in` / `packed` may be NULL only when no byte can be read (width 0, or
+ * packed_bytes == 0); `in` / `packed`, `mask` and `block_aggs` are 16-byte aligned (FL_ERR_ALIGN), and so is `result`.
+ * block_aggs / result are declared `void *` -- pass a `fl_block_aggregate *` as it is -- so that every prototype of this header keeps to
+ * the scalar types its language bindings map.
+ * (Declared by macros of their own: FL_DECLARE_TYPE's per-type list and the list of other functions are pinned surfaces.)
+ */
+typedef struct { uint64_t count, sum, min, max; } fl_block_aggregate;          /* 32 bytes */
+
+#define FL_DECLARE_AGGREGATE(T, S)                                                                        \
+    int fl_##S##_unfor_aggregate(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                 const uint32_t *mask /* may be NULL */, size_t n_blocks,                 \
+                                 void *block_aggs, uint32_t *err_flag, void *stream);                     \
+    int fl_##S##_unfor_aggregate_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,  \
+                                        size_t packed_bytes, const T *references, size_t reference_stride, \
+                                        const uint32_t *mask /* may be NULL */, size_t n_blocks,          \
+                                        void *block_aggs, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_AGGREGATE(uint8_t, u8)
+FL_DECLARE_AGGREGATE(uint16_t, u16)
+FL_DECLARE_AGGREGATE(uint32_t, u32)
+FL_DECLARE_AGGREGATE(uint64_t, u64)
+
+#define FL_DECLARE_AGGREGATE_REDUCE(NAME)                                                                 \
+    int fl_##NAME(const void *block_aggs, size_t n_blocks, void *result, void *stream);
+FL_DECLARE_AGGREGATE_REDUCE(aggregate_reduce)
+
 #ifdef __cplusplus
 }
 #endif

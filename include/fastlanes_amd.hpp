@@ -63,6 +63,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_compare_widths = fl_##S##_unfor_compare_widths;                  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
         static constexpr auto unfor_select_widths = fl_##S##_unfor_select_widths;                    \
+        static constexpr auto unfor_aggregate = fl_##S##_unfor_aggregate;                            \
+        static constexpr auto unfor_aggregate_widths = fl_##S##_unfor_aggregate_widths;              \
         static constexpr auto unpack_mixed = fl_##S##_unpack_mixed;                                  \
         static constexpr auto pack_mixed = fl_##S##_pack_mixed;                                      \
         static constexpr auto unpack_widths = fl_##S##_unpack_widths;                                \
@@ -198,6 +200,12 @@ template <typename T> struct FoR : BitPacking<T> {
                                     const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
                                     std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
     { detail::check(A::unfor_select((unsigned)width, d_packed, d_refs, ref_stride, d_mask, d_out_offsets, d_out, out_len, n_blocks, d_err_flag, stream), "unfor_select_device"); }
+    // count / sum / min / max per block of the values of unfor_pack(..) whose mask bit is set (d_mask == nullptr: of all of them), never
+    // materialised: d_block_aggs[b] for every block; aggregate_reduce_device combines them
+    static void unfor_aggregate_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
+                                       std::size_t n_blocks, fl_block_aggregate* d_block_aggs, std::uint32_t* d_err_flag = nullptr,
+                                       void* stream = nullptr)
+    { detail::check(A::unfor_aggregate((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_device"); }
 };
 
 // delta.rs:6-17
@@ -432,6 +440,16 @@ inline void unfor_select_widths_device(const std::uint8_t* d_widths, const std::
                                        const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
                                        std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_select_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, d_out_offsets, d_out, out_len, n_blocks, d_err_flag, stream), "unfor_select_widths"); }
+// ... or their count / sum / min / max per block, never materialised (d_mask == nullptr: every row); a block that fails the device checks
+// gets the identity {0, 0, UINT64_MAX, 0}
+template <typename T>
+inline void unfor_aggregate_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                          const T* d_references, std::size_t reference_stride, const std::uint32_t* d_mask, std::size_t n_blocks,
+                                          fl_block_aggregate* d_block_aggs, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_aggregate_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_widths"); }
+// per-block aggregates -> the column's: counts and sums added (wrapping), the smallest min, the largest max; no blocks: the identity
+inline void aggregate_reduce_device(const fl_block_aggregate* d_block_aggs, std::size_t n_blocks, fl_block_aggregate* d_result, void* stream = nullptr)
+{ detail::check(fl_aggregate_reduce(d_block_aggs, n_blocks, d_result, stream), "aggregate_reduce"); }
 template <typename T>
 inline void for_pack_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_in, const T* d_references,
                                    std::size_t reference_stride, T* d_packed, std::size_t packed_bytes, std::size_t n_blocks,

@@ -755,6 +755,127 @@ def main():
                 pair.free()
             torch.cuda.empty_cache()
         return
+    if args.cases == "aggregate":
+        # unfor_aggregate_widths (count / sum / min / max per block under a selection mask) over the mixed-width column of --cases mixed, at
+        # random mask densities 0 .. 100 % and with no mask.  Three yardsticks are timed in the SAME run on the SAME buffers, round-robin with
+        # the row under test: (1) a bare stream of the row's own bytes -- the mean packed bytes per block and, with a mask, 128 bytes in,
+        # 32 bytes out -- through fl_internal_bare_stream; (2) unfor_pack_widths of the column (the same packed reads, plus the
+        # 1024 * sizeof(T) bytes per block the aggregate does not write); (3) the composition the aggregate replaces: unfor_select_widths
+        # (offsets given) followed by a torch sum of the kept values.  Every figure is the median of `reps` launches with their min .. max
+        # beside it; the device's unique id heads the table.  aggregate_reduce (two launches) is timed on a line of its own, and once more
+        # at 10 M blocks.
+        import ctypes
+        lib = fl.load()
+        reps = max(args.reps, 5)
+        props = torch.cuda.get_device_properties(dev)
+        print(f"# device {props.name} unique id {getattr(props, 'uuid', 'unknown')}  placement {PLACEMENT}", flush=True)
+
+        def round_robin(variants):
+            """{name: [ms, ...]}: `reps` timed launches of every variant, interleaved, after two untimed rounds"""
+            for _ in range(2):
+                for f in variants.values():
+                    f()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in variants}
+            for _ in range(reps):
+                for k, f in variants.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); f(); b.record(); b.synchronize()
+                    ms[k].append(a.elapsed_time(b))
+            return ms
+
+        def random_mask(n, density, seed):
+            """int32 words of a random mask, built 32 Ki blocks at a time"""
+            g = torch.Generator(device=dev); g.manual_seed(seed)
+            out = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            sh = torch.arange(32, device=dev)
+            for b0 in range(0, n, 32768):
+                nb = min(32768, n - b0)
+                if density <= 0.0 or density >= 1.0:
+                    bits = torch.full((nb * 1024,), density >= 1.0, dtype=torch.bool, device=dev)
+                else:
+                    bits = torch.rand(nb * 1024, device=dev, generator=g) < density
+                w64 = (bits.view(-1, 32).to(torch.int64) << sh).sum(dim=1)
+                out[b0 * 32:(b0 + nb) * 32] = torch.where(w64 >= 1 << 31, w64 - (1 << 32), w64).to(torch.int32)
+            return out
+
+        def show(ms):
+            v = sorted(ms)
+            return f"{v[len(v) // 2]:9.4f} ms ({v[0]:.4f} .. {v[-1]:.4f})"
+
+        for ty in ("u32", "u64", "u16", "u8"):
+            if args.types and ty not in args.types.split(","):
+                continue
+            T, esz = ESZ[ty] * 8, ESZ[ty]
+            n = max(64, int(args.gb * 1e9 / (128 * T * 1.5)))
+            g = torch.Generator(device=dev); g.manual_seed(31 + T)
+            widths = torch.randint(1, T, (n,), dtype=torch.int64, device=dev, generator=g).to(torch.uint8)
+            offsets, total = fl.widths_to_offsets(ty, widths)
+            pbytes = int(total.item())
+            pair = None
+            if PLACEMENT == "interleaved":
+                from fastlanes_amd import placement as pl
+                pair = pl.ColumnPair(pbytes, n * 128 * T, dev, aux_bytes=n * 128, layout="interleaved")
+                print(f"# {ty}: constructed pair, measured classes (input first): {pair.classes}", flush=True)
+                col, un = pair.input.view(TDT[ty]), pair.output.view(TDT[ty])
+                col.view(torch.uint8).copy_(rnd(pbytes, 1))
+            else:
+                col = rnd(pbytes, 1).view(TDT[ty])
+                un = torch.empty(n * 1024, dtype=TDT[ty], device=dev)
+            refs = rnd(n * 8, 2).view(torch.uint8).view(-1, 8)[:, :esz].contiguous().view(TDT[ty]).reshape(-1)
+            slots = torch.empty((n, 4), dtype=torch.int64, device=dev)
+            agg_fn = getattr(lib, f"fl_{ty}_unfor_aggregate_widths")
+            Z, I = ctypes.c_size_t, ctypes.c_int
+            iu, au, ou, nt, wv, wn, bpu = Z(), Z(), Z(), I(), I(), I(), ctypes.c_uint()
+            mean_w2 = int(round(2 * float(widths.to(torch.float64).mean().item())))
+            assert lib.fl_internal_bare_stream_shape(3, T, mean_w2, *[ctypes.byref(x) for x in (iu, au, ou, nt, wv, wn, bpu)]) == 0
+            if pair is not None and pair.classes:
+                wn = I(31)                                 # inside a constructed pair the library launches under the whole-column tile map
+            nu = n // bpu.value
+            # the shape's unit comes from the ROUNDED mean width: never more than the column holds (the stream reads nu units back to back)
+            iu = Z(min(iu.value, pbytes // nu // 16 * 16))
+            assert 0 < iu.value <= 8192 and iu.value * nu <= pbytes and 128 * bpu.value <= 1024 and bpu.value * nu <= n
+            print(f"# {ty}: n = {n} blocks, packed {pbytes / 1e9:.2f} GB ({pbytes / n:.1f} B/block), {reps} launches each, round-robin; bare stream: "
+                  f"{iu.value} B in (+ {128 * bpu.value} B mask) and {32 * bpu.value} B out per unit of {bpu.value} block(s)", flush=True)
+            rows = [("empty", 0.0), ("1/1024", 1 / 1024), ("1 %", 0.01), ("50 %", 0.5), ("100 %", 1.0), ("mask=None", None)]
+            for name, density in rows:
+                mask = None if density is None else random_mask(n, density, 77 + T)
+                variants = {
+                    # the typed kernel alone, through the C ABI; "aggregate call" is the Python call: that launch plus aggregate_reduce's two
+                    "aggregate": lambda: agg_fn(widths.data_ptr(), offsets.data_ptr(), col.data_ptr(), pbytes, refs.data_ptr(), 1,
+                                                mask.data_ptr() if mask is not None else None, n, slots.data_ptr(), None, None),
+                    "aggregate call": lambda: fl.unfor_aggregate_widths(widths, offsets, col, refs, mask, block_aggs=slots, check=False),
+                    "bare": lambda: lib.fl_internal_bare_stream(col.data_ptr(), iu.value, mask.data_ptr() if mask is not None else None,
+                                                                128 * bpu.value if mask is not None else 0, slots.data_ptr(), 32 * bpu.value, nu,
+                                                                nt.value, wv.value, wn.value, None),
+                    "unfor_pack_widths": lambda: fl.unfor_pack_widths(widths, offsets, col, refs, output=un, check=False),
+                    "aggregate_reduce": lambda: fl.aggregate_reduce(slots),
+                }
+                if mask is not None:
+                    oo, tot = fl.mask_offsets(mask)
+                    kept = int(tot.item())
+                    variants["select + torch sum"] = lambda: fl.unfor_select_widths(widths, offsets, col, refs, mask, out_offsets=oo, total=tot, output=un,
+                                                                                    check=False)[:kept].sum(dtype=torch.int64)
+                else:
+                    kept = n * 1024
+                    variants["unfor_pack + torch sum"] = lambda: fl.unfor_pack_widths(widths, offsets, col, refs, output=un, check=False).sum(dtype=torch.int64)
+                ms = round_robin(variants)
+                med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+                agg = med["aggregate"]
+                print(f"unfor_aggregate_widths {name:10s} {ty:4s} kept {kept / (n * 1024):7.4f}  {show(ms['aggregate'])}  {n / agg / 1e6:8.3f} Gblocks/s", flush=True)
+                for k in variants:
+                    if k != "aggregate":
+                        print(f"    {k:24s} {ty:4s} {show(ms[k])}  {n / med[k] / 1e6:8.3f} Gblocks/s  aggregate x{agg / med[k]:.3f} of it", flush=True)
+                del mask, variants
+            del col, un, refs, slots
+            if pair is not None:
+                pair.free()
+            torch.cuda.empty_cache()
+        n = 10_000_000
+        slots = rnd(n * 32, 5).view(torch.int64).view(n, 4)
+        ms = round_robin({"aggregate_reduce": lambda: fl.aggregate_reduce(slots)})
+        print(f"aggregate_reduce {n} blocks  {show(ms['aggregate_reduce'])}  {n * 32 / sorted(ms['aggregate_reduce'])[reps // 2] / 1e6:8.1f} GB/s", flush=True)
+        return
     if args.cases == "single":
         # batched unpack_single (bitpacking.rs:132-200; benches/bitpacking.rs:36-65 times one lookup): k lookups into an n-block column
         # -- random, sorted, strided (one per block: every lookup a different block) and dense (all 1024 of consecutive blocks);
