@@ -920,7 +920,9 @@ def test_fused_transpose_extensions_vs_oracle_composition(fl, oracle, kernel_pol
 
 @pytest.mark.parametrize("ty", TYS)
 def test_fused_consumers_vs_oracle(fl, oracle, ty):
-    """unpack_block_sums / block_min_max (extensions): reductions of the oracle's outputs."""
+    """unpack_block_sums / block_min_max (extensions): reductions of the oracle's outputs.  (Random blocks hold their extremes several
+    times over, u8 ones about four times: whether block_min_max looks at EVERY position is checked in tests/test_gpu_extrema.py, on
+    blocks whose minimum and maximum sit at one position each.)"""
     T = tbits(ty)
     n = 37
     for w in range(T + 1):
