@@ -88,6 +88,24 @@ def for_compare_symbols():
     return [f"fl_{ty}_{m}" for ty in TYPES for m in _for_compare_signatures(ty)]
 
 
+def _for_compare_range_signatures(ty):
+    """FL_DECLARE_FOR_COMPARE_RANGE of include/fastlanes_amd.h (device tier): interval predicates chained through a mask."""
+    c = CTYPE[ty]
+    return {
+        "unfor_compare_range": [_U, _P, _P, _Z, c, c, ctypes.c_int, _P, _Z, _P, _P],
+        "unfor_compare_range_widths": [_P, _P, _P, _Z, _P, _Z, c, c, ctypes.c_int, _P, _Z, _P, _P, _P],
+    }
+
+
+def for_compare_range_symbols():
+    """The symbols FL_DECLARE_FOR_COMPARE_RANGE declares, all four element types."""
+    return [f"fl_{ty}_{m}" for ty in TYPES for m in _for_compare_range_signatures(ty)]
+
+
+# include/fastlanes_amd.h: fl_mask_combine
+MASK_COMBINE = {"new": 0, "and": 1, "or": 2}
+
+
 def _select_signatures(ty):
     """FL_DECLARE_SELECT of include/fastlanes_amd.h (device tier): only the rows a selection mask keeps, from FoR-packed columns."""
     return {
@@ -125,8 +143,8 @@ INTERNAL_SYMBOLS = ["fl_internal_set_kernel_policy", "fl_internal_get_kernel_pol
 
 def exported_symbols():
     """Every symbol include/fastlanes_amd.h and include/fastlanes_amd_internal.h declare, except FL_DECLARE_FOR_COMPARE's
-    (for_compare_symbols), FL_DECLARE_MASK_OFFSETS' / FL_DECLARE_SELECT's (select_symbols) and FL_DECLARE_AGGREGATE's /
-    FL_DECLARE_AGGREGATE_REDUCE's (aggregate_symbols)."""
+    (for_compare_symbols), FL_DECLARE_MASK_OFFSETS' / FL_DECLARE_SELECT's (select_symbols), FL_DECLARE_AGGREGATE's /
+    FL_DECLARE_AGGREGATE_REDUCE's (aggregate_symbols) and FL_DECLARE_FOR_COMPARE_RANGE's (for_compare_range_symbols)."""
     names = ["fl_version", "fl_status_string", "fl_last_hip_error", "fl_packed_len",
              "fl_mixed_plan_create", "fl_mixed_plan_destroy", "fl_mixed_plan_n_blocks",
              "fl_mixed_plan_packed_bytes", "fl_mixed_plan_offsets", "fl_mixed_plan_widths",
@@ -215,7 +233,8 @@ def load():
     lib.fl_aggregate_reduce.restype = ctypes.c_int
     lib.fl_aggregate_reduce.argtypes = [_P, _Z, _P, _P]
     for ty in TYPES:
-        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty), **_select_signatures(ty), **_aggregate_signatures(ty)}.items():
+        for m, argtypes in {**_signatures(ty), **_for_compare_signatures(ty), **_select_signatures(ty), **_aggregate_signatures(ty),
+                             **_for_compare_range_signatures(ty)}.items():
             fn = getattr(lib, f"fl_{ty}_{m}")
             fn.restype = ctypes.c_int
             fn.argtypes = argtypes

@@ -412,6 +412,42 @@ class FoR:
         return out
 
     @staticmethod
+    def unfor_compare_range(width, packed, reference, lo, hi, mask=None, combine="new", n_blocks=None, output=None):
+        """Interval predicate chained through a mask: with v = FoR.unfor_pack(width, block b, reference)[i] and all arithmetic mod 2^T,
+        hit = ((v - lo) mod 2^T) <= ((hi - lo) mod 2^T) -- the cyclic interval [lo, hi]: lo <= hi is BETWEEN, lo > hi wraps (v >= lo
+        OR v <= hi), hi == lo - 1 matches every value; predicate_interval gives the interval of a comparison, signed ones included.
+        combine "new": the result is hit (`mask` is ignored); "and" / "or": `mask` & hit / `mask` | hit, `mask` a CUDA int32 tensor of
+        32 words per block (the layout unfor_compare returns).  A block its reference and width decide, a block whose `mask` is all
+        zero under "and", and one whose `mask` is all ones under "or" are answered without reading their packed bytes.  `output` may
+        be `mask` itself (in place).  Device tier only; returns a CUDA int32 tensor of 32 words per block (`output` if given).
+        n_blocks is only needed for width == 0 without a mask or an output."""
+        import torch
+        cb = _range_combine(combine, mask)
+        if cb and _is_torch(mask) and _is_torch(packed) and 0 < width <= _lib.BITS[_ty_of(packed)] and \
+                mask.numel() * packed_len(_ty_of(packed), width) != 32 * packed.numel():
+            raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block of {packed_len(_ty_of(packed), width)} packed elements")
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_compare_range is device tier (pass CUDA tensors)")
+        if width > _lib.BITS[ty]:
+            raise FastLanesError(1, f"fl_{ty}_unfor_compare_range")
+        n = _blocks(src.n, packed_len(ty, width), "unfor_compare_range input")
+        if n is None:
+            n = n_blocks if n_blocks is not None else (mask.numel() // 32 if _is_torch(mask) and cb else
+                                                       (output.numel() // 32 if output is not None else 0))
+        m = _select_mask(src, mask, n) if cb else None
+        out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_range")
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        M = (1 << _lib.BITS[ty]) - 1
+        with torch.cuda.device(src.x.device):
+            _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare_range")(width, src.ptr, aux.ptr, stride, _lib.CTYPE[ty](int(lo) & M),
+                                                                        _lib.CTYPE[ty](int(hi) & M), cb, m.ptr if m is not None and n else None,
+                                                                        n, out.data_ptr(), _stream(src)),
+                   f"fl_{ty}_unfor_compare_range")
+        return out
+
+    @staticmethod
     def unfor_select(width, packed, reference, mask, out_offsets=None, total=None, n_blocks=None, output=None, check=True):
         """Only the rows a selection mask keeps: the values FoR.unfor_pack(width, packed, reference) yields where `mask` (the layout
         unfor_compare returns: a CUDA int32 tensor of 32 words per block, bit i of word i//32, LSB first) has a 1, compacted, in
@@ -699,6 +735,93 @@ def _select_mask(src, mask, n):
     if m.n != 32 * n:
         raise ValueError(f"mask holds {m.n} words, expected 32 per block = {32 * n}")
     return m
+
+
+def _range_combine(combine, mask):
+    """fl_mask_combine of a combine name; "and" / "or" need the mask so far."""
+    if combine not in _lib.MASK_COMBINE:
+        raise ValueError(f"combine must be one of {sorted(_lib.MASK_COMBINE)}")
+    cb = _lib.MASK_COMBINE[combine]
+    if cb and mask is None:
+        raise ValueError(f'combine="{combine}" needs the mask so far')
+    return cb
+
+
+def predicate_interval(ty, op, constant, signed=False):
+    """The cyclic interval (lo, hi) of bit patterns that satisfy `v <op> constant` for an element type ("u8" .. "u64") -- what
+    unfor_compare_range takes -- or None when no value satisfies it (x < 0 unsigned, x > the largest value, ...).  op is one of
+    '==', '!=', '<', '<=', '>', '>='.  signed=False compares unsigned (the constant is taken mod 2^T, as unfor_compare does);
+    signed=True reads the element type as two's complement, the constant within [-2^(T-1), 2^(T-1) - 1]: the signed order runs from
+    the pattern 2^(T-1) up through 2^T - 1, wraps to 0 and ends at 2^(T-1) - 1, so `x < k` is [2^(T-1), k - 1] -- a cyclic interval,
+    and every comparison of a signed column is one.  Pure Python, no GPU.
+    A predicate that no value satisfies has no interval: the caller skips the call and uses a zero mask under combine "new" / "and",
+    the mask so far under "or".  The complement of [lo, hi] is [hi + 1, lo - 1] (mod 2^T) unless the interval is full (hi == lo - 1),
+    whose complement is empty: NOT / AND-NOT are expressed through it."""
+    T = _lib.BITS[ty]
+    M = (1 << T) - 1
+    if op not in BitPacking.CMP:
+        raise ValueError(f"op must be one of {sorted(BitPacking.CMP)}")
+    k = int(constant)
+    if signed:
+        if not -(1 << (T - 1)) <= k < (1 << (T - 1)):
+            raise ValueError(f"constant {k} is not an i{T}")
+        first, last = 1 << (T - 1), (1 << (T - 1)) - 1       # the patterns of the smallest and the largest value
+    else:
+        first, last = 0, M
+    k &= M
+    if op == "==":
+        return k, k
+    if op == "!=":
+        return (k + 1) & M, (k - 1) & M
+    if op == "<":
+        return None if k == first else (first, (k - 1) & M)
+    if op == "<=":
+        return first, k
+    if op == ">":
+        return None if k == last else ((k + 1) & M, last)
+    return k, last
+
+
+def unfor_compare_range_widths(widths, offsets, packed, references, lo, hi, mask=None, combine="new", output=None, check=True):
+    """FoR.unfor_compare_range over a mixed-width column: the cyclic interval [lo, hi] (mod 2^T; predicate_interval gives a
+    comparison's) over the values unfor_pack_widths(widths, offsets, packed, references) yields, joined with the mask so far --
+    combine "new": the hits themselves (`mask` is ignored), "and" / "or": `mask` & hits / `mask` | hits.  `mask` and the result are
+    CUDA int32 tensors of 32 words per block (unfor_compare_widths' layout); `output` may be `mask` itself (in place).  A block its
+    reference and width decide, a block whose `mask` is all zero under "and", and one whose `mask` is all ones under "or" are
+    answered without reading their packed bytes -- so the later predicates of a chain read only the blocks the earlier ones left
+    open.  The per-block device checks of unfor_compare_widths, with the same contract: a block that fails them is skipped (its 32
+    mask words are left as they were); `check=True` reads the device error flag back (one sync) and raises, `check=False` stays
+    asynchronous."""
+    import torch
+    cb = _range_combine(combine, mask)
+    if cb and _is_torch(mask) and _is_torch(widths) and mask.numel() != 32 * widths.numel():
+        raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block = {32 * widths.numel()}")
+    src = _Arg(packed)
+    ty = src.ty
+    w = _Arg(widths, "u8")
+    o = _Arg(offsets, "u64")
+    _same_tier(src, w, o)
+    if not src.torch:
+        raise TypeError("unfor_compare_range_widths is device tier: widths, offsets and data must be CUDA tensors")
+    n = w.n
+    if o.n != n:
+        raise ValueError("offsets must hold one entry per block")
+    m = _select_mask(src, mask, n) if cb else None
+    r, (rptr, stride) = _block_references(src, ty, references, n)
+    out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_range_widths")
+    dev = src.x.device
+    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
+    M = (1 << _lib.BITS[ty]) - 1
+    with torch.cuda.device(dev):
+        _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare_range_widths")(w.ptr, o.ptr, src.ptr, pbytes, rptr, stride,
+                                                                           _lib.CTYPE[ty](int(lo) & M), _lib.CTYPE[ty](int(hi) & M), cb,
+                                                                           m.ptr if m is not None and n else None, n, out.data_ptr(),
+                                                                           err.data_ptr() if check else None, _stream(src)),
+               f"fl_{ty}_unfor_compare_range_widths")
+    if check:
+        _check_flag(err, f"fl_{ty}_unfor_compare_range_widths")   # bitpacking.rs:93,126 unreachable!(); :111-113
+    return out
 
 
 def mask_offsets(mask):

@@ -15,6 +15,7 @@
 #include "fl_scan.hpp"
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
+#include "fl_for_compare_range.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 
@@ -621,6 +622,51 @@ int run_unfor_compare(bool mixed, unsigned width, const uint8_t* widths, const u
     return hip_status(for_compare_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
+// unfor_compare_range over a uniform-width column (mixed = false) or a mixed-width one: run_unfor_compare with the cyclic interval
+// [lo, hi] as the predicate and the mask so far beside it (fl_for_compare_range.hpp).  The same launch shape, the same checks in the
+// same order; `mask` may be `mask_in`.
+template <typename T>
+int run_unfor_compare_range(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
+                            const T* refs, size_t ref_stride, T lo, T hi, int combine, const uint32_t* mask_in, size_t n_blocks,
+                            uint32_t* mask, uint32_t* err_flag, void* stream)
+{
+    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
+    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
+    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
+    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
+    else if (!mask_in) return FL_ERR_NULL;
+    if (!refs || !mask || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
+    const ForPredicate p = for_range_predicate(Elem<T>::BITS, lo, hi);
+    ForRangeArgs a;
+    a.packed = reinterpret_cast<const char*>(packed);
+    a.unpacked = nullptr;
+    a.widths = mixed ? widths : nullptr;
+    a.offsets = mixed ? offsets : nullptr;
+    a.err_flag = mixed ? err_flag : nullptr;
+    a.refs = nullptr;                        // the kernel loads cmp_refs with the block's metadata
+    a.ref_stride = ref_stride;
+    a.n_blocks = n_blocks;
+    a.uniform_width = mixed ? 0u : width;
+    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated here, on the host side
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
+    a.linear_map = 0;
+    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    a.mask = reinterpret_cast<char*>(mask);
+    a.cmp_refs = refs;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = 0u;
+    a.mask_in = reinterpret_cast<const char*>(mask_in);
+    a.combine = (unsigned)combine;
+    return hip_status(for_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
 // unfor_select over a uniform-width column (mixed = false) or a mixed-width one (widths[] / offsets[], checked per block by the kernel);
 // fl_select.hpp.  Launched with the shape of unfor_pack_widths, as unfor_compare is.
 template <typename T>
@@ -1140,6 +1186,19 @@ FL_DEFINE_AGGREGATE(uint8_t, u8)
 FL_DEFINE_AGGREGATE(uint16_t, u16)
 FL_DEFINE_AGGREGATE(uint32_t, u32)
 FL_DEFINE_AGGREGATE(uint64_t, u64)
+
+#define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                                 \
+    int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \
+                                     uint32_t* mask, void* s)                                             \
+    { FL_DEVICE_TIER(s, in, r, mi, mask); return run_unfor_compare_range<T>(false, w, nullptr, nullptr, in, 0, r, rs, lo, hi, cb, mi, n, mask, nullptr, s); } \
+    int fl_##S##_unfor_compare_range_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, T lo, T hi, \
+                                            int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
+    { FL_DEVICE_TIER(s, w, o, pk, r, mi, mask, ef); return run_unfor_compare_range<T>(true, 0, w, o, pk, pb, r, rs, lo, hi, cb, mi, n, mask, ef, s); }
+
+FL_DEFINE_FOR_COMPARE_RANGE(uint8_t, u8)
+FL_DEFINE_FOR_COMPARE_RANGE(uint16_t, u16)
+FL_DEFINE_FOR_COMPARE_RANGE(uint32_t, u32)
+FL_DEFINE_FOR_COMPARE_RANGE(uint64_t, u64)
 
 FL_DEFINE_TYPE(uint8_t, u8)
 FL_DEFINE_TYPE(uint16_t, u16)

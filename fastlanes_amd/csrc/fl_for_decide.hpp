@@ -48,6 +48,14 @@ FL_HD inline ForPredicate for_compare_predicate(unsigned type_bits, int op, uint
     }
 }
 
+// the cyclic interval [lo, hi] itself (unfor_compare_range): lo <= hi is BETWEEN, lo > hi wraps (v >= lo OR v <= hi), hi == lo - 1
+// is every value (s = M); never none.  A signed comparison is such an interval of the two's-complement bit patterns.
+FL_HD inline ForPredicate for_range_predicate(unsigned type_bits, uint64_t lo, uint64_t hi)
+{
+    const uint64_t M = type_max(type_bits);
+    return {lo & M, (hi - lo) & M, false};
+}
+
 // c = (r - a) mod 2^T of a block with reference r, and the block's verdict for fields of `width` bits (width <= type_bits)
 FL_HD inline int for_compare_decide(unsigned type_bits, const ForPredicate& p, uint64_t reference, unsigned width, uint64_t& c)
 {

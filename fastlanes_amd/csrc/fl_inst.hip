@@ -9,6 +9,7 @@
 //   13 unfor_compare (selection masks from FoR-packed columns, uniform or mixed width; fl_for_compare.hpp)
 //   14 unfor_select (only the rows a selection mask keeps, from the same columns; fl_select.hpp)
 //   15 unfor_aggregate (count / sum / min / max per block of the rows a mask keeps, from the same columns; fl_aggregate.hpp)
+//   16 unfor_compare_range (interval predicates over the same columns, chained through the mask so far; fl_for_compare_range.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -16,6 +17,7 @@
 #include "fl_batch.hpp"
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
+#include "fl_for_compare_range.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 
@@ -128,7 +130,9 @@ template <> for_compare_launch_t for_compare_launcher<T>() { return &launch_unfo
 template <> select_launch_t select_launcher<T>() { return &launch_unfor_select<T>; }
 #elif FL_FAMILY == 15
 template <> aggregate_launch_t aggregate_launcher<T>() { return &launch_unfor_aggregate<T>; }
+#elif FL_FAMILY == 16
+template <> for_range_launch_t for_range_launcher<T>() { return &launch_unfor_compare_range<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..15"
+#error "FL_FAMILY must be 0..6 or 8..16"
 #endif
 }  // namespace fl

@@ -401,6 +401,44 @@ FL_DECLARE_FOR_COMPARE(uint32_t, u32)
 FL_DECLARE_FOR_COMPARE(uint64_t, u64)
 
 /*
+ * EXTENSION: interval predicates chained through a mask -- WHERE ts BETWEEN a AND b AND status = 3 AND delta < 0 --
+ * over the same columns, uniform or mixed width.  Defined as the composition (all arithmetic mod 2^T)
+ *     v         = unfor_pack::<W_b>(block b, references[b*reference_stride])[i]                                  (ffor.rs:38-50)
+ *     hit[b][i] = ((v - lo) mod 2^T) <= ((hi - lo) mod 2^T)                    -- the cyclic interval [lo, hi]
+ *     FL_MASK_NEW: mask[b] = hit[b]   (mask_in ignored, may be NULL)
+ *     FL_MASK_AND: mask[b] = mask_in[b] & hit[b]          FL_MASK_OR: mask[b] = mask_in[b] | hit[b]
+ * lo <= hi is BETWEEN; lo > hi wraps and means v >= lo OR v <= hi; hi == lo - 1 matches every value.  Every unsigned fl_cmp
+ * predicate is such an interval (or matches nothing), and so is every SIGNED one over the two's-complement bit patterns: x < k is
+ * [2^(T-1), k - 1].  The complement of [lo, hi] is [hi + 1, lo - 1] unless the interval is full.  Masks have the layout of
+ * fl_<ty>_unpack_compare: 32 words per block, bit i % 32 of word b*32 + i/32.  Every valid block's 128 mask bytes are always written.
+ * `mask` may be the same pointer as `mask_in` (in place); ANY OTHER OVERLAP of the two is the caller's error.
+ * A block is answered without reading its packed bytes when its reference and width decide it (the rule of fl_<ty>_unfor_compare),
+ * when `combine` is AND and its mask_in is all zero, or when `combine` is OR and its mask_in is all ones.  The mixed-width form runs
+ * the per-block device checks of fl_<ty>_unfor_compare_widths with the same contract -- a failing block is skipped, its FL_DEVERR_*
+ * bit is ORed into *err_flag, its 32 mask words are left as they were -- so both can sit in one chain.
+ * width > T is FL_ERR_WIDTH (also for an empty column); a `combine` outside the enum FL_ERR_INDEX; n_blocks == 0 FL_OK; mask_in ==
+ * NULL with AND / OR, or any other required pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only when no byte can be read:
+ * width 0, or packed_bytes == 0); the packed column, `mask` and `mask_in` are 16-byte aligned (FL_ERR_ALIGN).
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+typedef enum fl_mask_combine { FL_MASK_NEW = 0, FL_MASK_AND = 1, FL_MASK_OR = 2 } fl_mask_combine;
+
+#define FL_DECLARE_FOR_COMPARE_RANGE(T, S)                                                                \
+    int fl_##S##_unfor_compare_range(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                     T lo, T hi, int combine, const uint32_t *mask_in /* NULL with FL_MASK_NEW */, \
+                                     size_t n_blocks, uint32_t *mask, void *stream);                      \
+    int fl_##S##_unfor_compare_range_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                            size_t packed_bytes, const T *references, size_t reference_stride, \
+                                            T lo, T hi, int combine, const uint32_t *mask_in /* NULL with FL_MASK_NEW */, \
+                                            size_t n_blocks, uint32_t *mask, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_FOR_COMPARE_RANGE(uint8_t, u8)
+FL_DECLARE_FOR_COMPARE_RANGE(uint16_t, u16)
+FL_DECLARE_FOR_COMPARE_RANGE(uint32_t, u32)
+FL_DECLARE_FOR_COMPARE_RANGE(uint64_t, u64)
+
+/*
  * EXTENSION (SURVEY.md 8(f2) "unpack -> filter", 8(f4) "take"): decode only the rows a selection mask keeps.  For a FoR-packed
  * column, uniform or mixed width, and a mask in the layout the compare entry points write (32 uint32 words per block, bit i of
  * block b = bit i % 32 of word b*32 + i/32, i in the unpacked index order):

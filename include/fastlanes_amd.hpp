@@ -61,6 +61,8 @@ template <typename T> struct Abi;
         static constexpr auto unpack_compare = fl_##S##_unpack_compare;                              \
         static constexpr auto unfor_compare = fl_##S##_unfor_compare;                                \
         static constexpr auto unfor_compare_widths = fl_##S##_unfor_compare_widths;                  \
+        static constexpr auto unfor_compare_range = fl_##S##_unfor_compare_range;                    \
+        static constexpr auto unfor_compare_range_widths = fl_##S##_unfor_compare_range_widths;      \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
         static constexpr auto unfor_select_widths = fl_##S##_unfor_select_widths;                    \
         static constexpr auto unfor_aggregate = fl_##S##_unfor_aggregate;                            \
@@ -195,6 +197,12 @@ template <typename T> struct FoR : BitPacking<T> {
     static void unfor_compare_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, fl_cmp op, T constant,
                                      std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
     { detail::check(A::unfor_compare((unsigned)width, d_packed, d_refs, ref_stride, (int)op, constant, n_blocks, d_mask, stream), "unfor_compare_device"); }
+    // the cyclic interval [lo, hi] (mod 2^T) over the same values, joined with the mask so far: FL_MASK_NEW (d_mask_in unused, may be
+    // nullptr), FL_MASK_AND, FL_MASK_OR; d_mask may be d_mask_in itself
+    static void unfor_compare_range_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, T lo, T hi,
+                                           fl_mask_combine combine, const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
+                                           void* stream = nullptr)
+    { detail::check(A::unfor_compare_range((unsigned)width, d_packed, d_refs, ref_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, stream), "unfor_compare_range_device"); }
     // only the values of unfor_pack(..) whose mask bit is set, compacted: block b's go to d_out[d_out_offsets[b] ..] (mask_offsets_device)
     static void unfor_select_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
                                     const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
@@ -429,6 +437,14 @@ inline void unfor_compare_widths_device(const std::uint8_t* d_widths, const std:
                                         const T* d_references, std::size_t reference_stride, fl_cmp op, T constant, std::size_t n_blocks,
                                         std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_compare_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, (int)op, constant, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_widths"); }
+// ... and an interval predicate chained through the mask so far: mask = [d_mask_in &, |] (value in the cyclic interval [lo, hi]); a block
+// the mask so far has already decided (all zero under AND, all ones under OR) is not read; d_mask may be d_mask_in itself
+template <typename T>
+inline void unfor_compare_range_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                              const T* d_references, std::size_t reference_stride, T lo, T hi, fl_mask_combine combine,
+                                              const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
+                                              std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_compare_range_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_range_widths"); }
 // selection mask -> where each block's kept values start in the compacted output (elements), and how many there are in all
 inline void mask_offsets_device(const std::uint32_t* d_mask, std::size_t n_blocks, std::uint64_t* d_out_offsets, std::uint64_t* d_total = nullptr,
                                 void* stream = nullptr)

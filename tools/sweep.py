@@ -876,6 +876,92 @@ def main():
         ms = round_robin({"aggregate_reduce": lambda: fl.aggregate_reduce(slots)})
         print(f"aggregate_reduce {n} blocks  {show(ms['aggregate_reduce'])}  {n * 32 / sorted(ms['aggregate_reduce'])[reps // 2] / 1e6:8.1f} GB/s", flush=True)
         return
+    if args.cases == "compare_range":
+        # unfor_compare_range_widths (an interval predicate chained through a mask) over the mixed-width column of --cases mixed, under the
+        # UNDECIDED predicate of that case (every block's value range straddles the constant, so no block is answered from its metadata and
+        # whatever is saved is saved by the incoming mask).  Timed in the SAME run on the SAME buffers, round-robin: NEW next to
+        # unfor_compare_widths; AND with an incoming mask of density 0, a clustered 1 % (one contiguous run of full blocks), a random 10 %
+        # (every block keeps something) and 100 %; the composition it replaces (unfor_compare_widths, then torch.bitwise_and with the mask so
+        # far); and unfor_compare_widths with every block decided (`x < 0`: metadata-only traffic).  Every figure is the median of `reps`
+        # launches with their min .. max beside it; the device's unique id heads the table.
+        reps = max(args.reps, 5)
+        props = torch.cuda.get_device_properties(dev)
+        print(f"# device {props.name} unique id {getattr(props, 'uuid', 'unknown')}  placement {PLACEMENT}", flush=True)
+
+        def round_robin(variants):
+            """{name: [ms, ...]}: `reps` timed launches of every variant, interleaved, after two untimed rounds"""
+            for _ in range(2):
+                for f in variants.values():
+                    f()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in variants}
+            for _ in range(reps):
+                for k, f in variants.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); f(); b.record(); b.synchronize()
+                    ms[k].append(a.elapsed_time(b))
+            return ms
+
+        def random_words(n, density, seed):
+            """int32 words of a random mask, built 32 Ki blocks at a time"""
+            g = torch.Generator(device=dev); g.manual_seed(seed)
+            out = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            sh = torch.arange(32, device=dev)
+            for b0 in range(0, n, 32768):
+                nb = min(32768, n - b0)
+                bits = torch.rand(nb * 1024, device=dev, generator=g) < density
+                w64 = (bits.view(-1, 32).to(torch.int64) << sh).sum(dim=1)
+                out[b0 * 32:(b0 + nb) * 32] = torch.where(w64 >= 1 << 31, w64 - (1 << 32), w64).to(torch.int32)
+            return out
+
+        def show(ms):
+            v = sorted(ms)
+            return f"{v[len(v) // 2]:9.4f} ms ({v[0]:.4f} .. {v[-1]:.4f})"
+
+        for ty in ("u32", "u64", "u16", "u8"):
+            if args.types and ty not in args.types.split(","):
+                continue
+            T, esz = ESZ[ty] * 8, ESZ[ty]
+            n = max(64, int(args.gb * 1e9 / (128 * T * 1.5)))
+            g = torch.Generator(device=dev); g.manual_seed(31 + T)
+            widths = torch.randint(1, T, (n,), dtype=torch.int64, device=dev, generator=g).to(torch.uint8)
+            offsets, total = fl.widths_to_offsets(ty, widths)
+            pbytes = int(total.item())
+            col = rnd(pbytes, 1).view(TDT[ty])
+            refs = rnd(n * 8, 2).view(torch.uint8).view(-1, 8)[:, :esz].contiguous().view(TDT[ty]).reshape(-1)
+            # references k - 1 - (x mod (2^W - 1)): every block's range [r, r + 2^W - 1] holds k - 1 and k, so `x < k` = [0, k - 1] decides none
+            k = 1 << (T - 1)
+            x = rnd(n * 8, 5).view(torch.int64) & ((1 << 62) - 1)
+            und = (k - 1) - x % ((torch.ones_like(x) << widths.to(torch.int64)) - 1)
+            refs_und = und.view(torch.uint8).view(-1, 8)[:, :esz].contiguous().view(TDT[ty]).reshape(-1)
+            lo, hi = 0, k - 1
+            out = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            hits = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            clustered = torch.zeros(n * 32, dtype=torch.int32, device=dev)
+            run = max(1, n // 100)
+            clustered[(n // 3) * 32:(n // 3 + run) * 32] = -1
+            masks = {"AND density 0": torch.zeros(n * 32, dtype=torch.int32, device=dev), "AND clustered 1 %": clustered,
+                     "AND random 10 %": random_words(n, 0.10, 77 + T), "AND density 100 %": torch.full((n * 32,), -1, dtype=torch.int32, device=dev)}
+            print(f"# {ty}: n = {n} blocks, packed {pbytes / 1e9:.2f} GB ({pbytes / n:.1f} B/block), {reps} launches each, round-robin", flush=True)
+            variants = {
+                "unfor_compare_widths undecided": lambda: fl.unfor_compare_widths(widths, offsets, col, refs_und, "<", k, output=out, check=False),
+                "NEW undecided": lambda: fl.unfor_compare_range_widths(widths, offsets, col, refs_und, lo, hi, output=out, check=False),
+                "compare all decided": lambda: fl.unfor_compare_widths(widths, offsets, col, refs, "<", 0, output=out, check=False),
+            }
+            for name, m in masks.items():
+                variants[name] = lambda m=m: fl.unfor_compare_range_widths(widths, offsets, col, refs_und, lo, hi, mask=m, combine="and", output=out,
+                                                                          check=False)
+            m10 = masks["AND random 10 %"]
+            variants["unfor_compare_widths + torch.bitwise_and"] = lambda: torch.bitwise_and(
+                fl.unfor_compare_widths(widths, offsets, col, refs_und, "<", k, output=hits, check=False), m10, out=out)
+            ms = round_robin(variants)
+            med = {kk: sorted(v)[len(v) // 2] for kk, v in ms.items()}
+            for kk in variants:
+                print(f"{kk:42s} {ty:4s} {show(ms[kk])}  {n / med[kk] / 1e6:8.3f} Gblocks/s  x{med[kk] / med['unfor_compare_widths undecided']:.3f} of undecided, "
+                      f"x{med[kk] / med['compare all decided']:.3f} of all decided", flush=True)
+            del col, refs, refs_und, out, hits, masks, clustered, m10, variants
+            torch.cuda.empty_cache()
+        return
     if args.cases == "single":
         # batched unpack_single (bitpacking.rs:132-200; benches/bitpacking.rs:36-65 times one lookup): k lookups into an n-block column
         # -- random, sorted, strided (one per block: every lookup a different block) and dense (all 1024 of consecutive blocks);
