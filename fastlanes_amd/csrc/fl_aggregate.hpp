@@ -4,7 +4,8 @@
 //     V_b   = [ unfor_pack::<W_b>(block b, references[b * ref_stride])[i]  for i if bit i of block b ]
 //     agg_b = { |V_b|, sum V_b (zero-extended to u64, wrapping), min V_b, max V_b }        (nothing kept: {0, 0, UINT64_MAX, 0})
 // (ffor.rs:38-50; the mask in unpack_compare's layout).  It reads 128*W packed bytes and 128 mask bytes per block and writes 32.
-// The wave-per-block machinery of fl_widths.hpp, as in fl_select.hpp:
+// The wave-per-block machinery of fl_widths.hpp, through the steps fl_for_block.hpp shares among the four consumers of a packed column
+// (the masks' stash is fl_select.hpp's):
 //   * a block's width, offset, reference AND the lane's mask slices arrive together (independent vector loads, one wait); its
 //     preconditions are checked (block_precondition): a failing block raises its bit and its slot receives the IDENTITY -- the slot feeds
 //     a reduction (fl_scan.hpp: launch_aggregate_reduce), so a skipped block must not leave stale memory in it;
@@ -17,9 +18,7 @@
 //   * lanes 0 and 1 store the slot's two 16-byte halves through a descriptor of exactly 32 bytes.
 // LDS is wave-local (in-order per wave): no s_barrier.  Every store is a vector store.
 #pragma once
-#include "fl_widths.hpp"
 #include "fl_for_compare.hpp"
-#include "fl_select_map.hpp"
 #include "fl_aggregate_map.hpp"
 
 namespace fl {
@@ -87,22 +86,11 @@ __device__ __forceinline__ BlockAggregate aggregate_lds_image(unsigned w, const 
     using G = WaveBlock<T>;
     using M = SelectMap<sizeof(T)>;
     using acc_t = typename AggregateLane<T>::acc_t;
-    constexpr int TB = G::TB;
     static_assert(M::GROUPS == (unsigned)G::GROUPS && M::N == (unsigned)Elem<T>::PER_CELL, "fl_select_map.hpp follows fl_widths.hpp's lane map");
-    const unsigned c16 = (lane & 7u) * 16u;
-    const typename G::word_t m = G::field_mask(w);
-    unsigned bit = __umul24(G::row_base(lane >> 3), w);
-    const unsigned step = G::KSTEP * w;
-    const unsigned last = (w - 1u) * 128u;
     const Cell<T> rc = Cell<T>::splat(ref);
     AggregateLane<T> l = aggregate_lane_of<T>(slice);
-    static_for<G::GROUPS>([&](auto K) {
-        const unsigned word = bit >> G::LOG_TB, sh = bit & (TB - 1u);
-        const unsigned a0 = word * 128u;
-        const unsigned a1 = a0 + 128u < last ? a0 + 128u : last;            // the last row never reads past the end (macros.rs:156)
-        const Cell<T> cur = __builtin_bit_cast(Cell<T>, *reinterpret_cast<const u32x4*>(lds + a0 + c16));
-        const Cell<T> nxt = __builtin_bit_cast(Cell<T>, *reinterpret_cast<const u32x4*>(lds + a1 + c16));
-        const Cell<T> v = G::funnel(cur, nxt, sh, m).add(rc);               // ffor.rs:46-48
+    for_each_funnelled_cell<T>(w, lds, lane, [&](auto K, unsigned bit, const Cell<T>& cell) {
+        const Cell<T> v = cell.add(rc);                                     // ffor.rs:46-48
         const uint32_t sl = slice[decltype(K)::value];
         static_for<(int)M::N>([&](auto E) {
             constexpr unsigned e = decltype(E)::value;
@@ -112,7 +100,6 @@ __device__ __forceinline__ BlockAggregate aggregate_lds_image(unsigned w, const 
             l.min = on && x < l.min ? x : l.min;
             l.max = on && x > l.max ? x : l.max;
         });
-        bit += step;
     });
     return aggregate_wave_reduce<T>(l);
 }
@@ -121,115 +108,57 @@ __device__ __forceinline__ BlockAggregate aggregate_lds_image(unsigned w, const 
 template <typename T>
 __device__ __forceinline__ void aggregate_block_wave(const AggregateArgs& a, uint64_t blk, char* lds, unsigned lane)
 {
-    using G = WaveBlock<T>;
     using M = SelectMap<sizeof(T)>;
-    constexpr int TB = G::TB;
-    const unsigned z = opaque_zero();
-    unsigned wv = a.uniform_width;
-    uint64_t ov = 0;
-    if (a.widths) wv = a.widths[blk + z];
-    if (a.offsets) ov = a.offsets[blk + z];
-    const T rv = static_cast<const T*>(a.agg_refs)[blk * a.ref_stride + z];
+    const BlockLoads<T> loads = issue_block_loads<T>(a, a.agg_refs, blk);
     uint32_t slice[M::GROUPS];
     static_for<(int)M::GROUPS>([&](auto K) {
         constexpr unsigned k = decltype(K)::value;
         slice[k] = (1u << M::N) - 1u;                                       // no mask: every row
         if (a.mask) slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
     });
-    const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(wv);
-    const uint64_t off = a.offsets ? wave_uniform_u64(ov) : blk * (uint64_t)(128u * w);
-    const T r = (T)wave_uniform_u64((uint64_t)rv);
-    if (const uint32_t e = block_precondition(a, w, off, TB)) {            // bitpacking.rs:126 unreachable!(), :111-113
-        raise_device_error(a.err_flag, e, lane);
+    const BlockMeta m = settle_block_loads<T>(a, blk, loads);
+    if (m.err) {
+        raise_device_error(a.err_flag, m.err, lane);
         store_block_aggregate(a, blk, aggregate_identity(), lane);
         return;
     }
     uint32_t any = 0;
     static_for<(int)M::GROUPS>([&](auto K) { any |= slice[decltype(K)::value]; });
     const bool empty = __builtin_amdgcn_ballot_w64(any != 0u) == 0ull;
-    if (empty || w == 0u) {                                                 // no packed load (fl_aggregate_map.hpp)
+    const T r = (T)m.r;
+    if (empty || m.w == 0u) {                                               // no packed load (fl_aggregate_map.hpp)
         const unsigned count = empty ? 0u : aggregate_wave_count(aggregate_lane_of<T>(slice).count);
         store_block_aggregate(a, blk, aggregate_constant_block(count, (uint64_t)r), lane);
         return;
     }
-    // wave-uniform descriptor over exactly this block's 128*w bytes: cells past it read as 0, no fault
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + off, 0, 128u * w, 0x00020000);
-    Cell<T> no_ref;
-    if (a.widths || w >= a.nt_from) packed_block_to_lds<T, RD_DMA_NT>(a, blk, rs, w, lds, lane, no_ref);   // RD_AUTO (fl_widths.hpp)
-    else packed_block_to_lds<T, RD_VGPR>(a, blk, rs, w, lds, lane, no_ref);
-    wave_lds_fence();
-    store_block_aggregate(a, blk, aggregate_lds_image<T>(w, lds, lane, r, slice), lane);
+    fill_block_image<T>(a, blk, m.off, m.w, lds, lane);
+    store_block_aggregate(a, blk, aggregate_lds_image<T>(m.w, lds, lane, r, slice), lane);
     wave_lds_fence();                                                       // the image is reused by the wavefront's next block
 }
 
-// the launch shapes aggregate_blocks_wave_static serves (any other shape runs block by block through the wavefront's first image)
-template <typename T> __host__ __device__ inline bool aggregate_static_shape(unsigned bpw, unsigned prefetch)
-{
-    return sizeof(T) <= 2 && prefetch != 0u && (bpw == 2u || bpw == 4u);
-}
-
-// BPW consecutive blocks per wavefront (the narrow types' shipped shapes), as select_blocks_wave_static: lane j judges block first + j --
-// metadata, reference, preconditions -- and the wavefront reads the BPW masks (two blocks per load) into `stash`, BEFORE any packed load
-// is issued; only the rows of the blocks that need a decode are then requested by LDS-DMA, one image per block, one wait, and the blocks
-// are aggregated back to back.  `stash`: BPW * 128 bytes of wave-private LDS behind the images.
+// BPW consecutive blocks per wavefront (the narrow types' shipped shapes: static_shape), as select_blocks_wave_static: lane j judges block
+// first + j -- metadata, reference, preconditions -- and the wavefront reads the BPW masks into its stash, BEFORE any packed load is
+// issued; only the rows of the blocks that need a decode are then requested by LDS-DMA, one image per block, one wait, and the blocks
+// are aggregated back to back.
 template <typename T, unsigned BPW>
 __device__ __forceinline__ void aggregate_blocks_wave_static(const AggregateArgs& a, uint64_t first, char* lds, uint32_t* stash, unsigned lane)
 {
     using G = WaveBlock<T>;
     using M = SelectMap<sizeof(T)>;
-    constexpr int TB = G::TB;
-    static_assert(BPW >= 2 && BPW <= 16 && BPW % 2 == 0, "two blocks' masks per load");
-    const bool owner = lane < BPW;
-    const uint64_t mine = first + (owner ? lane : 0u);
-    unsigned wv = a.uniform_width;
-    if (a.widths) wv = a.widths[mine];
-    uint64_t ov = mine * (uint64_t)(128u * wv);
-    if (a.offsets) ov = a.offsets[mine];
-    const T rv = static_cast<const T*>(a.agg_refs)[mine * a.ref_stride];
-    uint32_t mw[BPW / 2];
-    static_for<(int)(BPW / 2)>([&](auto I) {
-        constexpr unsigned i = decltype(I)::value;
-        mw[i] = ~0u;                                                        // no mask: every row
-        if (a.mask) mw[i] = a.mask[(first + 2u * i) * SELECT_MASK_WORDS + lane];   // words of blocks first + 2i (lanes 0..31) and first + 2i + 1
-    });
-    const uint32_t ev = block_precondition(a, wv, ov, TB);
-    unsigned nonempty = 0;                                                  // wave-uniform: bit j = block first + j keeps something
-    static_for<(int)(BPW / 2)>([&](auto I) {
-        constexpr unsigned i = decltype(I)::value;
-        stash[i * 64u + lane] = mw[i];
-        const uint64_t nz = __builtin_amdgcn_ballot_w64(mw[i] != 0u);
-        nonempty |= ((uint32_t)nz != 0u ? 1u : 0u) << (2u * i) | ((uint32_t)(nz >> 32) != 0u ? 2u : 0u) << (2u * i);
-    });
-    const uint64_t valid = __builtin_amdgcn_ballot_w64(owner && ev == 0u);
-    const uint64_t fetch = valid & nonempty;                                // (a width-0 block requests nothing: 8 * g < 0 never holds)
-    static_for<(int)BPW>([&](auto J) {
-        constexpr unsigned j = decltype(J)::value;
-        if ((fetch >> j) & 1u) {
-            const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wv, (int)j);
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + readlane_u64(ov, j), 0, 128u * w, 0x00020000);
-            char* img = lds + j * G::BLOCK_BYTES;
-            static_for<G::GROUPS>([&](auto Gi) {
-                constexpr int g = decltype(Gi)::value;
-                if (8u * g < w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(rs, img, lane);
-            });
-        }
-    });
-    wait_lds_dma();
-    wave_lds_fence();
+    const LaneBlocks<T> l = lane_block_loads<T>(a, a.agg_refs, first, BPW, lane);
+    const unsigned nonempty = stash_block_masks<BPW>(a.mask, first, stash, lane);
+    request_block_images<T, BPW>(a, l, __builtin_amdgcn_ballot_w64(l.owner && l.ev == 0u) & nonempty, lds, lane);
     for (unsigned j = 0; j < BPW; ++j) {                                    // wave-uniform loop
         const uint64_t blk = first + j;
-        if (const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)ev, (int)j)) {   // bitpacking.rs:126 unreachable!(), :111-113
+        if (const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)l.ev, (int)j)) {
             raise_device_error(a.err_flag, e, lane);
             store_block_aggregate(a, blk, aggregate_identity(), lane);
             continue;
         }
-        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wv, (int)j);
-        const T r = readlane_elem<T>(rv, j);
+        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)l.wv, (int)j);
+        const T r = readlane_elem<T>(l.rv, j);
         uint32_t slice[M::GROUPS];
-        static_for<(int)M::GROUPS>([&](auto K) {
-            constexpr unsigned k = decltype(K)::value;
-            slice[k] = M::slice(stash[j * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-        });
+        stashed_slices<T>(stash, j, lane, slice);
         const bool empty = !((nonempty >> j) & 1u);
         if (empty || w == 0u) {                                             // nothing was fetched (fl_aggregate_map.hpp)
             const unsigned count = empty ? 0u : aggregate_wave_count(aggregate_lane_of<T>(slice).count);
@@ -245,10 +174,8 @@ __global__ __launch_bounds__(WG) void k_unfor_aggregate(AggregateArgs a)
 {
     for_each_block_of_wave<T>(a, [&](uint64_t first, unsigned count, char* lds, unsigned lane) {
         if constexpr (sizeof(T) <= 2) {                       // the shipped shapes of the narrow types; any other shape: block by block
-            if (aggregate_static_shape<T>(a.bpw, a.prefetch) && count == a.bpw) {
-                extern __shared__ __attribute__((aligned(16))) char lds_all[];
-                const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-                uint32_t* stash = reinterpret_cast<uint32_t*>(lds_all + (WG / 64) * WaveBlock<T>::BLOCK_BYTES * a.bpw) + wave * a.bpw * SELECT_MASK_WORDS;
+            if (static_shape<T>(a.bpw, a.prefetch) && count == a.bpw) {
+                uint32_t* stash = wave_mask_stash<T>(a.bpw);
                 if (a.bpw == 4) aggregate_blocks_wave_static<T, 4>(a, first, lds, stash, lane);
                 else aggregate_blocks_wave_static<T, 2>(a, first, lds, stash, lane);
                 return;
@@ -258,20 +185,7 @@ __global__ __launch_bounds__(WG) void k_unfor_aggregate(AggregateArgs a)
     });
 }
 
-// Launched with the shape of unfor_pack_widths (the C ABI passes fl_dispatch.hpp's mixed_* choices through with_policy); the tile map is
-// plan_blocks', rotated for mixed-width columns as in launch_widths.  The masks' stash rides behind the workgroup's block images.
-typedef hipError_t (*aggregate_launch_t)(const AggregateArgs&, int waves, hipStream_t);
-template <typename T> hipError_t launch_unfor_aggregate(const AggregateArgs& a0, int waves, hipStream_t s)
-{
-    if (a0.n_blocks == 0) return hipSuccess;
-    AggregateArgs a = a0;
-    const unsigned need = tidy_wave_blocks<T>(a.bpw, a.prefetch) + (aggregate_static_shape<T>(a.bpw, a.prefetch) ? (WG / 64) * a.bpw * SELECT_MASK_WORDS * 4u : 0u);
-    const unsigned grid = plan_blocks(a, a.n_blocks, a.bpw * (WG / 64), WIN_UNPACK, WaveBlock<T>::TB, a.widths != nullptr);
-    const unsigned lds = occupancy_lds(waves, need);
-    if (!grid || lds > 64 * 1024) return hipErrorInvalidValue;         // > 2^33 blocks; beyond the default dynamic-LDS limit
-    FL_LAUNCH((k_unfor_aggregate<T>), dim3(grid), dim3(WG), lds, s, a);
-    return hipGetLastError();
-}
+typedef hipError_t (*aggregate_launch_t)(const AggregateArgs&, int waves, hipStream_t);   // launch_block_consumer (fl_for_block.hpp), with the stash
 template <typename T> aggregate_launch_t aggregate_launcher();
 
 }  // namespace fl

@@ -581,6 +581,45 @@ int run_chain_widths(int op, const uint8_t* widths, const uint64_t* offsets, con
     return rc >= 0 ? rc : hip_fail(hipErrorInvalidDeviceFunction);
 }
 
+// The four consumers of a FoR-packed column (fl_for_block.hpp): unfor_compare, unfor_compare_range, unfor_select, unfor_aggregate, each over
+// a uniform-width column (mixed = false: `width`, blocks back to back) or a mixed-width one (widths[] / offsets[], checked per block by the
+// kernel).  16 aligned zero bytes stand in for a buffer that has none.
+template <typename T> const T* no_bytes()
+{
+    static const T zeros[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
+    return zeros;
+}
+// false: one of the column's pointers is missing (FL_ERR_NULL).  A mixed-width column whose blocks all have width 0 has no packed bytes:
+// its packed pointer may be NULL (run_widths) and is replaced here.
+template <typename T>
+bool block_consumer_column(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T*& packed, size_t packed_bytes, const T* refs)
+{
+    if (mixed && !packed && packed_bytes == 0) packed = no_bytes<T>();
+    return refs && (!mixed || (widths && offsets)) && (packed || (!mixed && width == 0));
+}
+// the WidthsArgs part of the four argument blocks, launched with the shape of unfor_pack_widths: the same blocks, the same reads
+template <typename T>
+WaveShape block_consumer_args(WidthsArgs& a, bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed,
+                              size_t packed_bytes, size_t ref_stride, size_t n_blocks, uint32_t* err_flag)
+{
+    a.packed = reinterpret_cast<const char*>(packed);
+    a.unpacked = nullptr;
+    a.widths = mixed ? widths : nullptr;
+    a.offsets = mixed ? offsets : nullptr;
+    a.err_flag = err_flag;
+    a.refs = nullptr;                        // the kernel loads the references with the block's metadata
+    a.ref_stride = ref_stride;
+    a.n_blocks = n_blocks;
+    a.uniform_width = mixed ? 0u : width;
+    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated on the host side
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
+    a.linear_map = 0;
+    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    return sh;
+}
+
 // unfor_compare over a uniform-width column (mixed = false: `width`, blocks back to back) or a mixed-width one (widths[] / offsets[],
 // checked per block by the kernel); fl_for_compare.hpp.  The predicate becomes its cyclic interval here, once per call.
 template <typename T>
@@ -591,29 +630,11 @@ int run_unfor_compare(bool mixed, unsigned width, const uint8_t* widths, const u
     if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (op < FL_CMP_EQ || op > FL_CMP_GE) return FL_ERR_INDEX;
     if (n_blocks == 0) return FL_OK;
-    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
-    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
-    if (!refs || !mask || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !mask) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask)) return FL_ERR_ALIGN;
     const ForPredicate p = for_compare_predicate(Elem<T>::BITS, op, constant);
     ForCompareArgs a;
-    a.packed = reinterpret_cast<const char*>(packed);
-    a.unpacked = nullptr;
-    a.widths = mixed ? widths : nullptr;
-    a.offsets = mixed ? offsets : nullptr;
-    a.err_flag = mixed ? err_flag : nullptr;
-    a.refs = nullptr;                        // the kernel loads cmp_refs with the block's metadata
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = mixed ? 0u : width;
-    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated here, on the host side
-    // the shape of unfor_pack_widths: the same blocks, the same reads, a mask of 1/T of its writes
-    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
-    a.bpw = sh.bpw;
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, mixed ? err_flag : nullptr);
     a.mask = reinterpret_cast<char*>(mask);
     a.cmp_refs = refs;
     a.cmp_a = p.a;
@@ -633,30 +654,13 @@ int run_unfor_compare_range(bool mixed, unsigned width, const uint8_t* widths, c
     if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
     if (n_blocks == 0) return FL_OK;
-    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
-    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
     if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
     else if (!mask_in) return FL_ERR_NULL;
-    if (!refs || !mask || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !mask) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
     const ForPredicate p = for_range_predicate(Elem<T>::BITS, lo, hi);
     ForRangeArgs a;
-    a.packed = reinterpret_cast<const char*>(packed);
-    a.unpacked = nullptr;
-    a.widths = mixed ? widths : nullptr;
-    a.offsets = mixed ? offsets : nullptr;
-    a.err_flag = mixed ? err_flag : nullptr;
-    a.refs = nullptr;                        // the kernel loads cmp_refs with the block's metadata
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = mixed ? 0u : width;
-    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated here, on the host side
-    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
-    a.bpw = sh.bpw;
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, mixed ? err_flag : nullptr);
     a.mask = reinterpret_cast<char*>(mask);
     a.cmp_refs = refs;
     a.cmp_a = p.a;
@@ -676,30 +680,13 @@ int run_unfor_select(bool mixed, unsigned width, const uint8_t* widths, const ui
 {
     if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (n_blocks == 0) return FL_OK;
-    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
-    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
     // a selection that keeps nothing has no output: `out` may be NULL with out_len == 0 (a non-empty block then fails the kernel's
     // bounds check; nothing is ever written through this pointer)
-    if (!out && out_len == 0) out = const_cast<T*>(no_bytes);
-    if (!refs || !mask || !out_offsets || !out || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (!out && out_len == 0) out = const_cast<T*>(no_bytes<T>());
+    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !mask || !out_offsets || !out) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask) || misaligned(out)) return FL_ERR_ALIGN;
     SelectArgs a;
-    a.packed = reinterpret_cast<const char*>(packed);
-    a.unpacked = nullptr;
-    a.widths = mixed ? widths : nullptr;
-    a.offsets = mixed ? offsets : nullptr;
-    a.err_flag = err_flag;                   // the uniform form raises FL_DEVERR_BOUNDS too (a run outside `out`)
-    a.refs = nullptr;                        // the kernel loads sel_refs with the block's metadata
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = mixed ? 0u : width;
-    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated here, on the host side
-    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
-    a.bpw = sh.bpw;
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, err_flag);   // the uniform form raises FL_DEVERR_BOUNDS too (a run outside `out`)
     a.mask = mask;
     a.out_offsets = out_offsets;
     a.out = reinterpret_cast<char*>(out);
@@ -718,27 +705,10 @@ int run_unfor_aggregate(bool mixed, unsigned width, const uint8_t* widths, const
 {
     if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
     if (n_blocks == 0) return FL_OK;
-    // a mixed-width column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
-    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-    if (mixed && !packed && packed_bytes == 0) packed = no_bytes;
-    if (!refs || !block_aggs || (mixed && (!widths || !offsets)) || (!packed && (mixed || width != 0))) return FL_ERR_NULL;
+    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !block_aggs) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask) || misaligned(block_aggs)) return FL_ERR_ALIGN;
     AggregateArgs a;
-    a.packed = reinterpret_cast<const char*>(packed);
-    a.unpacked = nullptr;
-    a.widths = mixed ? widths : nullptr;
-    a.offsets = mixed ? offsets : nullptr;
-    a.err_flag = mixed ? err_flag : nullptr; // a uniform-width call is validated here, on the host side
-    a.refs = nullptr;                        // the kernel loads agg_refs with the block's metadata
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = mixed ? 0u : width;
-    a.packed_bytes = mixed ? packed_bytes : 0;
-    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
-    a.bpw = sh.bpw;
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, mixed ? err_flag : nullptr);
     a.mask = mask;
     a.aggs = static_cast<char*>(block_aggs);
     a.agg_refs = refs;

@@ -2,8 +2,9 @@
 // EXTENSION, defined as a composition of reference functions:
 //     bit i of mask[b*32 .. b*32+32) = (unfor_pack::<W_b>(block b, references[b * ref_stride])[i] <op> constant)
 // (ffor.rs:38-50; i in the unpacked index order, LSB first, 32 words per block: unpack_compare's layout, fl_consume.hpp).
-// The wave-per-block machinery of fl_widths.hpp (one wavefront per block, runtime width, the LDS image, WaveBlock::funnel) with
-// the predicate arithmetic of fl_for_decide.hpp:
+// The wave-per-block machinery of fl_widths.hpp (one wavefront per block, runtime width, the LDS image, WaveBlock::funnel), through
+// the steps fl_for_block.hpp shares among this kernel, unfor_compare_range, unfor_select and unfor_aggregate, with the predicate
+// arithmetic of fl_for_decide.hpp:
 //   * a block's width, offset AND reference arrive together (three vector loads, one wait -- block_ref loads the reference
 //     behind the data instead), its preconditions are checked (block_precondition: a failing block is skipped and its mask
 //     words are left untouched, as unpack_widths leaves its output), then the block is decided;
@@ -15,8 +16,7 @@
 //     128-byte store (lanes 0..7, 16 bytes each).
 // LDS is wave-local (in-order per wave): no s_barrier.  Every store is a vector store.
 #pragma once
-#include "fl_widths.hpp"
-#include "fl_consume.hpp"
+#include "fl_for_block.hpp"
 #include "fl_for_decide.hpp"
 
 namespace fl {
@@ -43,49 +43,28 @@ __device__ __forceinline__ void store_decided_mask(const ForCompareArgs& a, uint
     store_block_mask(a, blk, u32x4{m, m, m, m}, lane);
 }
 
-// The LDS image of an undecided block (1 <= w <= T rows) -> its mask.  Lane (i, c) holds, for 1-KiB group k, the cell of indices
-// [k*1024/sizeof(T) + lane*N, + N), N = 16/sizeof(T): bits at the same positions of the block's 1024-bit mask.  u8 / u16 write
-// their 16 / 8 bits as they are; u32 / u64 first join 2 / 4 neighbouring lanes' bits into a byte (DPP quad_perm, full wave).
+// The LDS image of an undecided block (1 <= w <= T rows) -> its verdicts: bit e of verdicts[k] = element e of the lane's cell of group k
+template <typename T>
+__device__ __forceinline__ void compare_image_verdicts(const ForCompareArgs& a, unsigned w, const char* lds, unsigned lane, T c,
+                                                       uint32_t (&verdicts)[WaveBlock<T>::GROUPS])
+{
+    constexpr int TB = WaveBlock<T>::TB;
+    const Cell<T> cc = Cell<T>::splat(c);
+    const T s = (T)a.cmp_s;
+    for_each_funnelled_cell<T>(w, lds, lane, [&](auto K, unsigned bit, const Cell<T>& cell) {
+        // ((f + c) mod 2^T) <= s per element: bit e = element e of the cell
+        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(cell.add(cc), s);
+    });
+}
+
+// The LDS image of an undecided block -> its mask: walk, gather (verdicts_to_image: the first 128 bytes of the by then dead image),
+// and ONE coalesced 128-byte store
 template <typename T>
 __device__ __forceinline__ void compare_lds_image(const ForCompareArgs& a, uint64_t blk, unsigned w, char* lds, unsigned lane, T c)
 {
-    using G = WaveBlock<T>;
-    constexpr int TB = G::TB;
-    constexpr unsigned N = Elem<T>::PER_CELL;
-    const unsigned c16 = (lane & 7u) * 16u;
-    const typename G::word_t m = G::field_mask(w);
-    unsigned bit = __umul24(G::row_base(lane >> 3), w);
-    const unsigned step = G::KSTEP * w;
-    const unsigned last = (w - 1u) * 128u;
-    const Cell<T> cc = Cell<T>::splat(c);
-    const T s = (T)a.cmp_s;
-    uint32_t verdicts[G::GROUPS];
-    static_for<G::GROUPS>([&](auto K) {
-        const unsigned word = bit >> G::LOG_TB, sh = bit & (TB - 1u);
-        const unsigned a0 = word * 128u;
-        const unsigned a1 = a0 + 128u < last ? a0 + 128u : last;            // the last row never reads past the end (macros.rs:156)
-        const Cell<T> cur = __builtin_bit_cast(Cell<T>, *reinterpret_cast<const u32x4*>(lds + a0 + c16));
-        const Cell<T> nxt = __builtin_bit_cast(Cell<T>, *reinterpret_cast<const u32x4*>(lds + a1 + c16));
-        // ((f + c) mod 2^T) <= s per element: bit e = element e of the cell
-        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(G::funnel(cur, nxt, sh, m).add(cc), s);
-        bit += step;
-    });
-    wave_lds_fence();                                                       // every lane holds its verdicts: the image is dead
-    static_for<G::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        uint32_t v = verdicts[k];
-        char* at = lds + k * (128u / sizeof(T)) + lane * N / 8u;            // byte of mask bit k*1024/sizeof(T) + lane*N
-        if constexpr (sizeof(T) == 1) {
-            *reinterpret_cast<uint16_t*>(at) = (uint16_t)v;
-        } else if constexpr (sizeof(T) == 2) {
-            *reinterpret_cast<uint8_t*>(at) = (uint8_t)v;
-        } else {
-            v |= butterfly_partner<0>(v) << N;                              // + lane ^ 1's bits
-            if constexpr (N == 2) v |= butterfly_partner<1>(v) << 4u;       // + lane ^ 2's (u64: 4 lanes per byte)
-            if ((lane & (8u / N - 1u)) == 0u) *reinterpret_cast<uint8_t*>(at) = (uint8_t)v;
-        }
-    });
-    wave_lds_fence();
+    uint32_t verdicts[WaveBlock<T>::GROUPS];
+    compare_image_verdicts<T>(a, w, lds, lane, c, verdicts);
+    verdicts_to_image<T>(verdicts, lds, lane);
     store_block_mask(a, blk, *reinterpret_cast<const u32x4*>(lds + lane * 16u), lane);
 }
 
@@ -93,42 +72,20 @@ __device__ __forceinline__ void compare_lds_image(const ForCompareArgs& a, uint6
 template <typename T>
 __device__ __forceinline__ void compare_block_wave(const ForCompareArgs& a, uint64_t blk, char* lds, unsigned lane)
 {
-    using G = WaveBlock<T>;
-    constexpr int TB = G::TB;
-    // widths[blk], offsets[blk] and the reference: independent vector loads in flight together, one wait, then wave-uniform
-    const unsigned z = opaque_zero();
-    unsigned wv = a.uniform_width;
-    uint64_t ov = 0;
-    if (a.widths) wv = a.widths[blk + z];
-    if (a.offsets) ov = a.offsets[blk + z];
-    const T rv = static_cast<const T*>(a.cmp_refs)[blk * a.ref_stride + z];
-    const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(wv);
-    const uint64_t off = a.offsets ? wave_uniform_u64(ov) : blk * (uint64_t)(128u * w);
-    const uint64_t r = wave_uniform_u64((uint64_t)rv);
-    if (const uint32_t e = block_precondition(a, w, off, TB)) {            // bitpacking.rs:126 unreachable!(), :111-113
-        raise_device_error(a.err_flag, e, lane);
+    const BlockMeta m = settle_block_loads<T>(a, blk, issue_block_loads<T>(a, a.cmp_refs, blk));
+    if (m.err) {
+        raise_device_error(a.err_flag, m.err, lane);
         return;
     }
     uint64_t c;
-    const int verdict = for_compare_decide(TB, predicate_of(a), r, w, c);
+    const int verdict = for_compare_decide(WaveBlock<T>::TB, predicate_of(a), m.r, m.w, c);
     if (verdict != FOR_CMP_EACH) {                                          // (W = 0 always ends here)
         store_decided_mask(a, blk, verdict, lane);
         return;
     }
-    // wave-uniform descriptor over exactly this block's 128*w bytes: cells past it read as 0, no fault
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + off, 0, 128u * w, 0x00020000);
-    Cell<T> no_ref;
-    if (a.widths || w >= a.nt_from) packed_block_to_lds<T, RD_DMA_NT>(a, blk, rs, w, lds, lane, no_ref);   // RD_AUTO (fl_widths.hpp)
-    else packed_block_to_lds<T, RD_VGPR>(a, blk, rs, w, lds, lane, no_ref);
-    wave_lds_fence();
-    compare_lds_image<T>(a, blk, w, lds, lane, (T)c);
+    fill_block_image<T>(a, blk, m.off, m.w, lds, lane);
+    compare_lds_image<T>(a, blk, m.w, lds, lane, (T)c);
     wave_lds_fence();                                                       // the image is reused by the wavefront's next block
-}
-
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, unsigned j)
-{
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
 }
 
 // Several consecutive blocks per wavefront (the narrow types), as unpack_blocks_wave_prefetched: lane j judges block first + j --
@@ -138,33 +95,13 @@ template <typename T>
 __device__ __forceinline__ void compare_blocks_wave_prefetched(const ForCompareArgs& a, uint64_t first, unsigned count, char* lds, unsigned lane)
 {
     using G = WaveBlock<T>;
-    constexpr int TB = G::TB;
-    const bool owner = lane < count;                          // count <= 16 <= 64 lanes
-    const uint64_t mine = first + (owner ? lane : 0u);
-    unsigned wv = a.uniform_width;
-    if (a.widths) wv = a.widths[mine];
-    uint64_t ov = mine * (uint64_t)(128u * wv);
-    if (a.offsets) ov = a.offsets[mine];
-    const T rv = static_cast<const T*>(a.cmp_refs)[mine * a.ref_stride];
-    const uint32_t ev = block_precondition(a, wv, ov, TB);
+    const LaneBlocks<T> l = lane_block_loads<T>(a, a.cmp_refs, first, count, lane);
     uint64_t cv = 0;
-    const int vv = ev ? (int)FOR_CMP_EACH : for_compare_decide(TB, predicate_of(a), rv, wv, cv);
-    const uint64_t fetch = __builtin_amdgcn_ballot_w64(owner && ev == 0u && vv == FOR_CMP_EACH);
+    const int vv = l.ev ? (int)FOR_CMP_EACH : for_compare_decide(G::TB, predicate_of(a), l.rv, l.wv, cv);
+    request_block_images<T>(a, l, __builtin_amdgcn_ballot_w64(l.owner && l.ev == 0u && vv == FOR_CMP_EACH), count, lds, lane);
     for (unsigned j = 0; j < count; ++j) {                    // wave-uniform loop
-        if (!((fetch >> j) & 1u)) continue;
-        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wv, (int)j);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + readlane_u64(ov, j), 0, 128u * w, 0x00020000);
-        char* img = lds + j * G::BLOCK_BYTES;
-        static_for<G::GROUPS>([&](auto Gi) {
-            constexpr int g = decltype(Gi)::value;
-            if (8u * g < w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(rs, img, lane);
-        });
-    }
-    wait_lds_dma();
-    wave_lds_fence();
-    for (unsigned j = 0; j < count; ++j) {
         const uint64_t blk = first + j;
-        if (const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)ev, (int)j)) {   // bitpacking.rs:126 unreachable!(), :111-113
+        if (const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)l.ev, (int)j)) {
             raise_device_error(a.err_flag, e, lane);
             continue;
         }
@@ -173,7 +110,7 @@ __device__ __forceinline__ void compare_blocks_wave_prefetched(const ForCompareA
             store_decided_mask(a, blk, verdict, lane);
             continue;
         }
-        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wv, (int)j);
+        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)l.wv, (int)j);
         compare_lds_image<T>(a, blk, w, lds + j * G::BLOCK_BYTES, lane, (T)readlane_u64(cv, j));
     }
 }
@@ -190,20 +127,7 @@ __global__ __launch_bounds__(WG) void k_unfor_compare(ForCompareArgs a)
     });
 }
 
-// Launched with the shape of unfor_pack_widths (the C ABI passes fl_dispatch.hpp's mixed_* choices through with_policy); the
-// tile map is plan_blocks', rotated for mixed-width columns as in launch_widths.
-typedef hipError_t (*for_compare_launch_t)(const ForCompareArgs&, int waves, hipStream_t);
-template <typename T> hipError_t launch_unfor_compare(const ForCompareArgs& a0, int waves, hipStream_t s)
-{
-    if (a0.n_blocks == 0) return hipSuccess;
-    ForCompareArgs a = a0;
-    const unsigned need = tidy_wave_blocks<T>(a.bpw, a.prefetch);
-    const unsigned grid = plan_blocks(a, a.n_blocks, a.bpw * (WG / 64), WIN_UNPACK, WaveBlock<T>::TB, a.widths != nullptr);
-    const unsigned lds = occupancy_lds(waves, need);
-    if (!grid || lds > 64 * 1024) return hipErrorInvalidValue;         // > 2^33 blocks; beyond the default dynamic-LDS limit
-    FL_LAUNCH((k_unfor_compare<T>), dim3(grid), dim3(WG), lds, s, a);
-    return hipGetLastError();
-}
+typedef hipError_t (*for_compare_launch_t)(const ForCompareArgs&, int waves, hipStream_t);   // launch_block_consumer (fl_for_block.hpp)
 template <typename T> for_compare_launch_t for_compare_launcher();
 
 }  // namespace fl

@@ -9,9 +9,9 @@
 //     hold 16 bytes each -- the shape store_block_mask stores in;
 //   * a block is answered WITHOUT a packed load when for_compare_decide decides it from reference and width, when the combiner is
 //     AND and its incoming mask is all zero, or when the combiner is OR and its incoming mask is all ones (one ballot serves both);
-//   * an undecided block gathers its verdict bits in the dead LDS image as compare_lds_image does (those lines are copied, not
-//     shared: the compare kernel's code stays as it is), and they are combined with the lane's 16 bytes just before the one
-//     coalesced 128-byte store;
+//   * an undecided block gathers its verdict bits in the dead LDS image through compare_lds_image's own walk and gather
+//     (compare_image_verdicts, verdicts_to_image), and they are combined with the lane's 16 bytes just before the one coalesced
+//     128-byte store;
 //   * a block that fails the mixed-width device checks is skipped: its FL_DEVERR_* bit is raised, its mask words are left alone.
 // Every valid block's 128 bytes are always written.  `mask` may be `mask_in` itself: a wavefront has read the incoming masks of all
 // the blocks it owns before it stores the first of them, and no other wavefront touches those bytes.
@@ -54,74 +54,32 @@ __device__ __forceinline__ void store_decided_range(const ForRangeArgs& a, uint6
     store_range_mask(a, blk, range_combine(a.combine, in, u32x4{m, m, m, m}), lane, base);
 }
 
-// compare_lds_image with the incoming mask: `in` = the 16 bytes lanes base .. base + 7 hold of block `blk`'s mask_in
+// The LDS image of an undecided block -> its mask: compare_lds_image's walk and gather, then the verdict bits are combined with `in`
+// = the 16 bytes lanes base .. base + 7 hold of block `blk`'s mask_in
 template <typename T>
-__device__ __forceinline__ void range_lds_image(const ForRangeArgs& a, uint64_t blk, unsigned w, char* lds, unsigned lane, T c, u32x4 in, unsigned base)
+__device__ __forceinline__ void combine_lds_image(const ForRangeArgs& a, uint64_t blk, unsigned w, char* lds, unsigned lane, T c, u32x4 in, unsigned base)
 {
-    using G = WaveBlock<T>;
-    constexpr int TB = G::TB;
-    constexpr unsigned N = Elem<T>::PER_CELL;
-    const unsigned c16 = (lane & 7u) * 16u;
-    const typename G::word_t m = G::field_mask(w);
-    unsigned bit = __umul24(G::row_base(lane >> 3), w);
-    const unsigned step = G::KSTEP * w;
-    const unsigned last = (w - 1u) * 128u;
-    const Cell<T> cc = Cell<T>::splat(c);
-    const T s = (T)a.cmp_s;
-    uint32_t verdicts[G::GROUPS];
-    static_for<G::GROUPS>([&](auto K) {
-        const unsigned word = bit >> G::LOG_TB, sh = bit & (TB - 1u);
-        const unsigned a0 = word * 128u;
-        const unsigned a1 = a0 + 128u < last ? a0 + 128u : last;            // the last row never reads past the end (macros.rs:156)
-        const Cell<T> cur = __builtin_bit_cast(Cell<T>, *reinterpret_cast<const u32x4*>(lds + a0 + c16));
-        const Cell<T> nxt = __builtin_bit_cast(Cell<T>, *reinterpret_cast<const u32x4*>(lds + a1 + c16));
-        // ((f + c) mod 2^T) <= s per element: bit e = element e of the cell
-        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(G::funnel(cur, nxt, sh, m).add(cc), s);
-        bit += step;
-    });
-    wave_lds_fence();                                                       // every lane holds its verdicts: the image is dead
-    static_for<G::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        uint32_t v = verdicts[k];
-        char* at = lds + k * (128u / sizeof(T)) + lane * N / 8u;            // byte of mask bit k*1024/sizeof(T) + lane*N
-        if constexpr (sizeof(T) == 1) {
-            *reinterpret_cast<uint16_t*>(at) = (uint16_t)v;
-        } else if constexpr (sizeof(T) == 2) {
-            *reinterpret_cast<uint8_t*>(at) = (uint8_t)v;
-        } else {
-            v |= butterfly_partner<0>(v) << N;                              // + lane ^ 1's bits
-            if constexpr (N == 2) v |= butterfly_partner<1>(v) << 4u;       // + lane ^ 2's (u64: 4 lanes per byte)
-            if ((lane & (8u / N - 1u)) == 0u) *reinterpret_cast<uint8_t*>(at) = (uint8_t)v;
-        }
-    });
-    wave_lds_fence();
-    // lane base + i reads the 16 bytes lane i of the compare kernel stores (c16 = (lane & 7) * 16; base is a multiple of 8)
-    store_range_mask(a, blk, range_combine(a.combine, in, *reinterpret_cast<const u32x4*>(lds + c16)), lane, base);
+    uint32_t verdicts[WaveBlock<T>::GROUPS];
+    compare_image_verdicts<T>(a, w, lds, lane, c, verdicts);
+    verdicts_to_image<T>(verdicts, lds, lane);
+    // lane base + i reads the 16 bytes lane i of the compare kernel stores (base is a multiple of 8)
+    store_range_mask(a, blk, range_combine(a.combine, in, *reinterpret_cast<const u32x4*>(lds + (lane & 7u) * 16u)), lane, base);
 }
 
 // one block per call: metadata, reference and the incoming mask in flight together; only an open block requests its packed rows
 template <typename T>
 __device__ __forceinline__ void range_block_wave(const ForRangeArgs& a, uint64_t blk, char* lds, unsigned lane)
 {
-    using G = WaveBlock<T>;
-    constexpr int TB = G::TB;
-    const unsigned z = opaque_zero();
-    unsigned wv = a.uniform_width;
-    uint64_t ov = 0;
-    if (a.widths) wv = a.widths[blk + z];
-    if (a.offsets) ov = a.offsets[blk + z];
-    const T rv = static_cast<const T*>(a.cmp_refs)[blk * a.ref_stride + z];
+    const BlockLoads<T> loads = issue_block_loads<T>(a, a.cmp_refs, blk);
     u32x4 in = {0u, 0u, 0u, 0u};
     if (a.combine != MASK_NEW) {
         // exactly this block's 128 bytes: lanes 8..63 read past the descriptor, which returns 0 and touches no memory
         const __amdgpu_buffer_rsrc_t ms = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.mask_in) + blk * 128u, 0, 128u, 0x00020000);
         in = __builtin_amdgcn_raw_buffer_load_b128(ms, lane * 16u, 0, 0);
     }
-    const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(wv);
-    const uint64_t off = a.offsets ? wave_uniform_u64(ov) : blk * (uint64_t)(128u * w);
-    const uint64_t r = wave_uniform_u64((uint64_t)rv);
-    if (const uint32_t e = block_precondition(a, w, off, TB)) {            // bitpacking.rs:126 unreachable!(), :111-113
-        raise_device_error(a.err_flag, e, lane);
+    const BlockMeta m = settle_block_loads<T>(a, blk, loads);
+    if (m.err) {
+        raise_device_error(a.err_flag, m.err, lane);
         return;
     }
     if (__builtin_amdgcn_ballot_w64(lane < 8u && range_mask_live(a.combine, in)) == 0ull) {
@@ -129,18 +87,13 @@ __device__ __forceinline__ void range_block_wave(const ForRangeArgs& a, uint64_t
         return;
     }
     uint64_t c;
-    const int verdict = for_compare_decide(TB, predicate_of(a), r, w, c);
+    const int verdict = for_compare_decide(WaveBlock<T>::TB, predicate_of(a), m.r, m.w, c);
     if (verdict != FOR_CMP_EACH) {                                          // (W = 0 always ends here)
         store_decided_range(a, blk, verdict, in, lane, 0u);
         return;
     }
-    // wave-uniform descriptor over exactly this block's 128*w bytes: cells past it read as 0, no fault
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + off, 0, 128u * w, 0x00020000);
-    Cell<T> no_ref;
-    if (a.widths || w >= a.nt_from) packed_block_to_lds<T, RD_DMA_NT>(a, blk, rs, w, lds, lane, no_ref);   // RD_AUTO (fl_widths.hpp)
-    else packed_block_to_lds<T, RD_VGPR>(a, blk, rs, w, lds, lane, no_ref);
-    wave_lds_fence();
-    range_lds_image<T>(a, blk, w, lds, lane, (T)c, in, 0u);
+    fill_block_image<T>(a, blk, m.off, m.w, lds, lane);
+    combine_lds_image<T>(a, blk, m.w, lds, lane, (T)c, in, 0u);
     wave_lds_fence();                                                       // the image is reused by the wavefront's next block
 }
 
@@ -152,14 +105,7 @@ template <typename T>
 __device__ __forceinline__ void range_blocks_wave_prefetched(const ForRangeArgs& a, uint64_t first, unsigned count, char* lds, unsigned lane)
 {
     using G = WaveBlock<T>;
-    constexpr int TB = G::TB;
-    const bool owner = lane < count;                          // count <= 16 <= 64 lanes
-    const uint64_t mine = first + (owner ? lane : 0u);
-    unsigned wv = a.uniform_width;
-    if (a.widths) wv = a.widths[mine];
-    uint64_t ov = mine * (uint64_t)(128u * wv);
-    if (a.offsets) ov = a.offsets[mine];
-    const T rv = static_cast<const T*>(a.cmp_refs)[mine * a.ref_stride];
+    const LaneBlocks<T> l = lane_block_loads<T>(a, a.cmp_refs, first, count, lane);
     u32x4 in[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};      // in[h]: 16 bytes of block first + 8h + lane / 8
     uint64_t live[2] = {~0ull, ~0ull};
     if (a.combine != MASK_NEW) {
@@ -170,29 +116,16 @@ __device__ __forceinline__ void range_blocks_wave_prefetched(const ForRangeArgs&
         live[0] = __builtin_amdgcn_ballot_w64(range_mask_live(a.combine, in[0]));
         live[1] = __builtin_amdgcn_ballot_w64(range_mask_live(a.combine, in[1]));
     }
-    const uint32_t ev = block_precondition(a, wv, ov, TB);
     uint64_t cv = 0;
-    const int vv = ev ? (int)FOR_CMP_EACH : for_compare_decide(TB, predicate_of(a), rv, wv, cv);
+    const int vv = l.ev ? (int)FOR_CMP_EACH : for_compare_decide(G::TB, predicate_of(a), l.rv, l.wv, cv);
     // bit j: block first + j's answer is still open after its incoming mask (byte j % 8 of live[j / 8])
     unsigned open_blocks = 0;
     for (unsigned j = 0; j < count; ++j)                      // wave-uniform
         open_blocks |= (((live[j >> 3] >> (8u * (j & 7u))) & 0xffull) != 0ull ? 1u : 0u) << j;
-    const uint64_t fetch = __builtin_amdgcn_ballot_w64(owner && ev == 0u && vv == FOR_CMP_EACH) & open_blocks;
+    request_block_images<T>(a, l, __builtin_amdgcn_ballot_w64(l.owner && l.ev == 0u && vv == FOR_CMP_EACH) & open_blocks, count, lds, lane);
     for (unsigned j = 0; j < count; ++j) {                    // wave-uniform loop
-        if (!((fetch >> j) & 1u)) continue;
-        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wv, (int)j);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + readlane_u64(ov, j), 0, 128u * w, 0x00020000);
-        char* img = lds + j * G::BLOCK_BYTES;
-        static_for<G::GROUPS>([&](auto Gi) {
-            constexpr int g = decltype(Gi)::value;
-            if (8u * g < w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(rs, img, lane);
-        });
-    }
-    wait_lds_dma();
-    wave_lds_fence();
-    for (unsigned j = 0; j < count; ++j) {
         const uint64_t blk = first + j;
-        if (const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)ev, (int)j)) {   // bitpacking.rs:126 unreachable!(), :111-113
+        if (const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)l.ev, (int)j)) {
             raise_device_error(a.err_flag, e, lane);
             continue;
         }
@@ -207,8 +140,8 @@ __device__ __forceinline__ void range_blocks_wave_prefetched(const ForRangeArgs&
             store_decided_range(a, blk, verdict, mi, lane, base);
             continue;
         }
-        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wv, (int)j);
-        range_lds_image<T>(a, blk, w, lds + j * G::BLOCK_BYTES, lane, (T)readlane_u64(cv, j), mi, base);
+        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)l.wv, (int)j);
+        combine_lds_image<T>(a, blk, w, lds + j * G::BLOCK_BYTES, lane, (T)readlane_u64(cv, j), mi, base);
     }
 }
 
@@ -224,19 +157,7 @@ __global__ __launch_bounds__(WG) void k_unfor_compare_range(ForRangeArgs a)
     });
 }
 
-// Launched with the shape of unfor_pack_widths, exactly as k_unfor_compare is (launch_unfor_compare).
-typedef hipError_t (*for_range_launch_t)(const ForRangeArgs&, int waves, hipStream_t);
-template <typename T> hipError_t launch_unfor_compare_range(const ForRangeArgs& a0, int waves, hipStream_t s)
-{
-    if (a0.n_blocks == 0) return hipSuccess;
-    ForRangeArgs a = a0;
-    const unsigned need = tidy_wave_blocks<T>(a.bpw, a.prefetch);
-    const unsigned grid = plan_blocks(a, a.n_blocks, a.bpw * (WG / 64), WIN_UNPACK, WaveBlock<T>::TB, a.widths != nullptr);
-    const unsigned lds = occupancy_lds(waves, need);
-    if (!grid || lds > 64 * 1024) return hipErrorInvalidValue;         // > 2^33 blocks; beyond the default dynamic-LDS limit
-    FL_LAUNCH((k_unfor_compare_range<T>), dim3(grid), dim3(WG), lds, s, a);
-    return hipGetLastError();
-}
+typedef hipError_t (*for_range_launch_t)(const ForRangeArgs&, int waves, hipStream_t);   // launch_block_consumer (fl_for_block.hpp)
 template <typename T> for_range_launch_t for_range_launcher();
 
 }  // namespace fl

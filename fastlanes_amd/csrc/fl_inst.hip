@@ -125,13 +125,13 @@ template <> const CompareTable<T>& compare_table_impl<T, false>() { return t_com
 static constexpr CompareTable<T> t_compare_eq = make_compare_table<T, true>(Ws{});
 template <> const CompareTable<T>& compare_table_impl<T, true>() { return t_compare_eq; }
 #elif FL_FAMILY == 13
-template <> for_compare_launch_t for_compare_launcher<T>() { return &launch_unfor_compare<T>; }
+template <> for_compare_launch_t for_compare_launcher<T>() { return &launch_block_consumer<T, ForCompareArgs, k_unfor_compare<T>, false>; }
 #elif FL_FAMILY == 14
-template <> select_launch_t select_launcher<T>() { return &launch_unfor_select<T>; }
+template <> select_launch_t select_launcher<T>() { return &launch_block_consumer<T, SelectArgs, k_unfor_select<T>, true>; }
 #elif FL_FAMILY == 15
-template <> aggregate_launch_t aggregate_launcher<T>() { return &launch_unfor_aggregate<T>; }
+template <> aggregate_launch_t aggregate_launcher<T>() { return &launch_block_consumer<T, AggregateArgs, k_unfor_aggregate<T>, true>; }
 #elif FL_FAMILY == 16
-template <> for_range_launch_t for_range_launcher<T>() { return &launch_unfor_compare_range<T>; }
+template <> for_range_launch_t for_range_launcher<T>() { return &launch_block_consumer<T, ForRangeArgs, k_unfor_compare_range<T>, false>; }
 #else
 #error "FL_FAMILY must be 0..6 or 8..16"
 #endif

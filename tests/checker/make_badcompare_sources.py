@@ -13,7 +13,7 @@ only boundary-dense data reaches (tests/test_gpu_compare_boundaries.py, profiles
    compares [field | junk] with [k | zeros] instead of [k | ones] -- wrong where field == k and the row below left a set bit.
 2. u8 / u16 unpack_compare (compare_block_lds, InPlaceRows): `<` for `<=` in rank class 1, where every in-place field of the 32-bit
    register equals k (28 bits or more of coincidence: u8 W = 1, u16 W in {1, 2, 3, 5, 7}).
-3. unfor_compare / unfor_compare_widths (fl_for_compare.hpp: compare_lds_image): `(f + c) < s` for `<= s` in rows >= 1 at W >= 25
+3. unfor_compare / unfor_compare_widths (fl_for_compare.hpp: compare_image_verdicts, which unfor_compare_range shares): `(f + c) < s` for `<= s` in rows >= 1 at W >= 25
    (W = 24 is what test_encoder_chain_ascending_column_is_mostly_decided[u32] happens to hold next to its `== v[777]`).
 Never loaded by anything but `FL_LIB=.../libfastlanes_amd_badcompare.so pytest tests/test_gpu_compare_boundaries.py ...`.  Every
 replacement below must match the current source exactly once, or this script fails: a refactor has to carry the patch along."""
@@ -49,9 +49,9 @@ PATCHES = {
     ],
     "fl_for_compare.hpp": [
         # 3. `< s` for `<= s` in rows >= 1 (bit = row * w, w >= 1)
-        ("        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(G::funnel(cur, nxt, sh, m).add(cc), s);\n",
-         "        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(G::funnel(cur, nxt, sh, m).add(cc), s) &\n"
-         "            ~((w >= 25u && bit != 0u) ? row_predicate_bits<T, TB, true>(G::funnel(cur, nxt, sh, m).add(cc), s) : 0u);   // KNOWN-BAD\n"),
+        ("        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(cell.add(cc), s);\n",
+         "        verdicts[decltype(K)::value] = row_predicate_bits<T, TB, false>(cell.add(cc), s) &\n"
+         "            ~((w >= 25u && bit != 0u) ? row_predicate_bits<T, TB, true>(cell.add(cc), s) : 0u);   // KNOWN-BAD\n"),
     ],
 }
 for name, patches in PATCHES.items():

@@ -66,7 +66,7 @@ def test_a_changed_needle_is_refused(tmp_path):
         if f.endswith((".hpp", ".hip", ".inc")):
             text = open(os.path.join(CSRC, f)).read()
             if f == "fl_for_compare.hpp":
-                text = text.replace("row_predicate_bits<T, TB, false>(G::funnel(cur, nxt, sh, m).add(cc), s);", "row_predicate_bits<T, TB, false>(G::funnel(cur, nxt, sh, m).add(cc),  s);")
+                text = text.replace("row_predicate_bits<T, TB, false>(cell.add(cc), s);", "row_predicate_bits<T, TB, false>(cell.add(cc),  s);")
             (src / f).write_text(text)
     r = subprocess.run([sys.executable, SCRIPT, str(src), str(tmp_path / "out")], capture_output=True, text=True)
     assert r.returncode != 0 and "no longer holds exactly one copy" in r.stderr
