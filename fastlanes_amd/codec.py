@@ -75,6 +75,25 @@ def _check_flag(err, where):
         raise FastLanesError(5, where)
 
 
+class _Flag:
+    """The device error flag of one call: a zeroed int32 word on `device` when the caller asked for the check (none otherwise),
+    `ptr` for the C argument (None: the kernel reports nothing), `raise_if_set` after the launch -- the one sync of a checked call."""
+
+    def __init__(self, check, device):
+        import torch
+        self.err = torch.zeros(1, dtype=torch.int32, device=device) if check else None
+        self.ptr = self.err.data_ptr() if check else None
+
+    def raise_if_set(self, where):
+        if self.err is not None:
+            _check_flag(self.err, where)
+
+
+def _scalar(ty, value):
+    """A Python int reduced mod 2^T, as the element type's C scalar (signed ints are reinterpreted, never refused)."""
+    return _lib.CTYPE[ty](int(value) & ((1 << _lib.BITS[ty]) - 1))
+
+
 def _indices(index, like):
     """Column-global element indices for the device tier: a CUDA int64/uint64 tensor on `like`'s device (anything
     else is converted from the host).  A float tensor, or one of another device, would be reinterpreted / fault."""
@@ -128,9 +147,39 @@ def _empty_like(arg, n, ty):
     return np.empty(n, dtype=_NP_DTYPE[ty])
 
 
-def _stream(arg):
+def _stream(device):
     import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(arg.x.device).cuda_stream)
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _launch(name, device, *args, stream=True):
+    """THE call into the C ABI: fetch `name` (`name`_host on the host tier, device=None), append the current HIP stream of `device`
+    (stream=False: an entry point that takes none), call, and turn a non-zero status into FastLanesError.  The library launches on
+    the calling thread's CURRENT device, so a tensor of another device is entered first -- and the stream is read inside that
+    context; the common case, the tensor's device already current, skips the context switch."""
+    fn = getattr(_lib.load(), name if device is not None else name + "_host")
+    if device is None:
+        rc = fn(*args)
+    else:
+        import torch
+        if device.index == torch.cuda.current_device():
+            rc = fn(*args, _stream(device)) if stream else fn(*args)
+        else:
+            with torch.cuda.device(device):
+                rc = fn(*args, _stream(device)) if stream else fn(*args)
+    _check(rc, name)
+
+
+def _single_call(name, src, index, *lead):
+    """The device tier of the two point lookups: `lead`, then (indices, n_indices, out, err_flag, stream).  The flag is always read
+    back: an index past the column is the reference's assert (bitpacking.rs:152)."""
+    import torch
+    idx = _indices(index, src)
+    out = torch.empty(idx.numel(), dtype=src.x.dtype, device=src.x.device)
+    flag = _Flag(True, src.x.device)
+    _launch(name, src.x.device, *lead, idx.data_ptr(), idx.numel(), out.data_ptr(), flag.ptr)
+    flag.raise_if_set(name)
+    return out
 
 
 def _same_tier(src, *others):
@@ -177,10 +226,8 @@ def _consumer_out(src, output, dtype, n_elems, what):
 
 def _run(method, ty, width, src, out, n_blocks, aux=None, aux_stride=None, scalar=None):
     """Dispatch to fl_<ty>_<method>[_host]."""
-    lib = _lib.load()
     dev = src.torch
     _same_tier(src, out, aux)
-    fn = getattr(lib, f"fl_{ty}_{method}" + ("" if dev else "_host"))
     args = []
     if width is not None:
         args.append(width)
@@ -192,28 +239,52 @@ def _run(method, ty, width, src, out, n_blocks, aux=None, aux_stride=None, scala
             args.append(scalar)
     elif aux is not None:
         args.append(aux.ptr)
-    args += [out.ptr, n_blocks]
-    if dev:
-        import torch
-        if src.x.device.index == torch.cuda.current_device():   # common case: skip the device context switch
-            args.append(_stream(src))
-            rc = fn(*args)
-        else:
-            with torch.cuda.device(src.x.device):
-                args.append(_stream(src))
-                rc = fn(*args)
-    else:
-        rc = fn(*args)
-    _check(rc, f"fl_{ty}_{method}")
+    _launch(f"fl_{ty}_{method}", src.x.device if dev else None, *args, out.ptr, n_blocks)
     return out.x
 
 
-def _blocks(n, per_block, what):
+def _blocks(n, per_block, method):
     if per_block == 0:
         return None
     if n % per_block:
-        raise ValueError(f"{what}: length {n} is not a multiple of {per_block}")
+        raise ValueError(f"{method} input: length {n} is not a multiple of {per_block}")
     return n // per_block
+
+
+def _check_width(ty, width, method):
+    """width > T is unreachable!() in the reference (bitpacking.rs:93,126,197): FL_ERR_WIDTH here, before anything is sized from it."""
+    if width > _lib.BITS[ty]:
+        raise FastLanesError(1, f"fl_{ty}_{method}")
+
+
+def _numel(x):
+    return x.numel() if _is_torch(x) else np.asarray(x).size
+
+
+def _uniform_blocks(src, width, method, n_blocks, *fallbacks):
+    """Block count of a uniform-width packed input: the width check, then the packed length divided by the packed block
+    (bitpacking.rs:77).  Width 0 packs to nothing, so the empty input says nothing: the count is then `n_blocks` if given, else that
+    of the first `fallbacks` entry (tensor or None, its elements per block) that is there, else 0."""
+    _check_width(src.ty, width, method)
+    n = _blocks(src.n, packed_len(src.ty, width), method)
+    if n is None:
+        n = n_blocks if n_blocks is not None else next((_numel(t) // per for t, per in fallbacks if t is not None), 0)
+    return n
+
+
+def _block_words(x, what, words, word_bytes, src=None, n=None):
+    """A per-block integer tensor of `words` `word_bytes`-byte words per block (a selection mask: 32 x 4, block aggregates: 4 x 8), on
+    `src`'s tier and device when given: the wrapped tensor and its block count, which must be `n` when given."""
+    a = _Arg(x)
+    if src is not None:
+        _same_tier(src, a)
+    if a.x.dtype.is_floating_point or a.x.element_size() != word_bytes:
+        raise TypeError(f"{what} must be an int{8 * word_bytes} / uint{8 * word_bytes} tensor ({words} words per block), got {a.x.dtype}")
+    if n is not None and a.n != words * n:
+        raise ValueError(f"{what} holds {a.n} words, expected {words} per block = {words * n}")
+    if a.n % words:
+        raise ValueError(f"{what} holds {a.n} words, not a multiple of {words} (one block)")
+    return a, a.n // words
 
 
 class BitPacking:
@@ -224,9 +295,8 @@ class BitPacking:
         """BitPacking::pack::<W> / unchecked_pack (bitpacking.rs:19,30,65-96)."""
         src = _Arg(input)
         ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_pack")
-        n = _blocks(src.n, 1024, "pack input")
+        _check_width(ty, width, "pack")
+        n = _blocks(src.n, 1024, "pack")
         out = _out(src, output, ty, n * packed_len(ty, width), "pack")     # bitpacking.rs:78
         return _run("pack", ty, width, src, out, n)
 
@@ -238,11 +308,7 @@ class BitPacking:
         n_blocks is only needed for width == 0 (the packed input is empty)."""
         src = _Arg(input)
         ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unpack")
-        n = _blocks(src.n, packed_len(ty, width), "unpack input")
-        if n is None:
-            n = n_blocks if n_blocks is not None else (_Arg(output, ty).n // 1024 if output is not None else 0)
+        n = _uniform_blocks(src, width, "unpack", n_blocks, (output, 1024))
         out = _out(src, output, ty, n * 1024, "unpack")                    # bitpacking.rs:112
         return _run("unpack", ty, width, src, out, n)
 
@@ -253,28 +319,16 @@ class BitPacking:
         """BitPacking::unpack_single::<W> / unchecked_unpack_single (bitpacking.rs:47,58,132-200).
         `index` is an int (host tier: returns an int) or, on the device tier, a CUDA int64/uint64
         tensor of column-global element indices (block*1024 + i): returns a tensor of values."""
-        lib = _lib.load()
         src = _Arg(packed)
         ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unpack_single")
+        _check_width(ty, width, "unpack_single")
         pl = packed_len(ty, width)
         nb = n_blocks if n_blocks is not None else (src.n // pl if pl else 1)
         if not src.torch:
             val = _lib.CTYPE[ty](0)
-            rc = getattr(lib, f"fl_{ty}_unpack_single_host")(width, src.ptr, nb, int(index), ctypes.byref(val))
-            _check(rc, f"fl_{ty}_unpack_single")
+            _launch(f"fl_{ty}_unpack_single", None, width, src.ptr, nb, int(index), ctypes.byref(val))
             return val.value
-        import torch
-        idx = _indices(index, src)
-        out = torch.empty(idx.numel(), dtype=src.x.dtype, device=src.x.device)
-        err = torch.zeros(1, dtype=torch.int32, device=src.x.device)
-        with torch.cuda.device(src.x.device):
-            rc = getattr(lib, f"fl_{ty}_unpack_single")(width, src.ptr, nb, idx.data_ptr(), idx.numel(),
-                                                        out.data_ptr(), err.data_ptr(), _stream(src))
-        _check(rc, f"fl_{ty}_unpack_single")
-        _check_flag(err, f"fl_{ty}_unpack_single")             # bitpacking.rs:152
-        return out
+        return _single_call(f"fl_{ty}_unpack_single", src, index, width, src.ptr, nb)
 
     unchecked_unpack_single = unpack_single
 
@@ -286,16 +340,9 @@ class BitPacking:
         of the uint64 sums) -- `output` (n_blocks 8-byte elements) if given."""
         import torch
         src = _Arg(packed)
-        ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unpack_block_sums")
-        n = _blocks(src.n, packed_len(ty, width), "unpack_block_sums input")
-        if n is None:
-            n = n_blocks or 0
+        n = _uniform_blocks(src, width, "unpack_block_sums", n_blocks)
         out = _consumer_out(src, output, torch.int64, n, "unpack_block_sums")
-        with torch.cuda.device(src.x.device):
-            _check(getattr(_lib.load(), f"fl_{ty}_unpack_block_sums")(width, src.ptr, n, out.data_ptr(), _stream(src)),
-                   f"fl_{ty}_unpack_block_sums")
+        _launch(f"fl_{src.ty}_unpack_block_sums", src.x.device, width, src.ptr, n, out.data_ptr())
         return out
 
     CMP = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
@@ -308,34 +355,22 @@ class BitPacking:
         LSB first) -- `output` (32 * n_blocks 4-byte elements) if given."""
         import torch
         src = _Arg(packed)
-        ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unpack_compare")
-        n = _blocks(src.n, packed_len(ty, width), "unpack_compare input")
-        if n is None:
-            n = n_blocks or 0
+        n = _uniform_blocks(src, width, "unpack_compare", n_blocks)
         out = _consumer_out(src, output, torch.int32, n * 32, "unpack_compare")
-        k = _lib.CTYPE[ty](int(constant) & ((1 << _lib.BITS[ty]) - 1))
-        with torch.cuda.device(src.x.device):
-            _check(getattr(_lib.load(), f"fl_{ty}_unpack_compare")(width, src.ptr, BitPacking.CMP[op], k, n,
-                                                                   out.data_ptr(), _stream(src)),
-                   f"fl_{ty}_unpack_compare")
+        _launch(f"fl_{src.ty}_unpack_compare", src.x.device, width, src.ptr, BitPacking.CMP[op], _scalar(src.ty, constant), n,
+                out.data_ptr())
         return out
 
     @staticmethod
     def block_min_max(values, output=None):
         """(mins, maxs) per 1024-value block of an unpacked column -- written into `output` = (mins, maxs), two CUDA tensors of
         n_blocks elements of the column's type, if given.  Device tier only."""
-        import torch
         src = _Arg(values)
-        ty = src.ty
-        n = _blocks(src.n, 1024, "block_min_max input")
+        n = _blocks(src.n, 1024, "block_min_max")
         mins, maxs = output if output is not None else (None, None)
         mins = _consumer_out(src, mins, src.x.dtype, n, "block_min_max mins")
         maxs = _consumer_out(src, maxs, src.x.dtype, n, "block_min_max maxs")
-        with torch.cuda.device(src.x.device):
-            _check(getattr(_lib.load(), f"fl_{ty}_block_min_max")(src.ptr, n, mins.data_ptr(), maxs.data_ptr(), _stream(src)),
-                   f"fl_{ty}_block_min_max")
+        _launch(f"fl_{src.ty}_block_min_max", src.x.device, src.ptr, n, mins.data_ptr(), maxs.data_ptr())
         return mins, maxs
 
 
@@ -345,7 +380,7 @@ class FoR:
     @staticmethod
     def _ref(src, ty, reference, n):
         if not src.torch:
-            return None, None, _lib.CTYPE[ty](int(reference) & ((1 << _lib.BITS[ty]) - 1))
+            return None, None, _scalar(ty, reference)
         import torch
         if _is_torch(reference):
             r = _Arg(reference.contiguous(), ty)
@@ -353,7 +388,7 @@ class FoR:
             if r.n not in (1, n):
                 raise ValueError("references must hold 1 or n_blocks elements")
             return r, (0 if r.n == 1 else 1), None
-        host = np.array([int(reference) & ((1 << _lib.BITS[ty]) - 1)], dtype=_NP_DTYPE[ty])
+        host = np.array([_scalar(ty, reference).value], dtype=_NP_DTYPE[ty])
         r = torch.from_numpy(host.view(np.uint8)).to(src.x.device).view(src.x.dtype)
         return _Arg(r, ty), 0, None
 
@@ -362,9 +397,8 @@ class FoR:
         """FoR::for_pack::<W> (ffor.rs:5-9,24-36)."""
         src = _Arg(input)
         ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_for_pack")
-        n = _blocks(src.n, 1024, "for_pack input")
+        _check_width(ty, width, "for_pack")
+        n = _blocks(src.n, 1024, "for_pack")
         out = _out(src, output, ty, n * packed_len(ty, width), "for_pack")
         aux, stride, scalar = FoR._ref(src, ty, reference, n)
         return _run("for_pack", ty, width, src, out, n, aux=aux, aux_stride=stride, scalar=scalar)
@@ -374,11 +408,7 @@ class FoR:
         """FoR::unfor_pack::<W> (ffor.rs:11-17,38-50)."""
         src = _Arg(input)
         ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unfor_pack")
-        n = _blocks(src.n, packed_len(ty, width), "unfor_pack input")
-        if n is None:   # width 0: the packed input is empty -- take the block count from n_blocks or the output
-            n = n_blocks if n_blocks is not None else (_Arg(output, ty).n // 1024 if output is not None else 0)
+        n = _uniform_blocks(src, width, "unfor_pack", n_blocks, (output, 1024))
         out = _out(src, output, ty, n * 1024, "unfor_pack")
         aux, stride, scalar = FoR._ref(src, ty, reference, n)
         return _run("unfor_pack", ty, width, src, out, n, aux=aux, aux_stride=stride, scalar=scalar)
@@ -397,18 +427,11 @@ class FoR:
         ty = src.ty
         if not src.torch:
             raise TypeError("unfor_compare is device tier (pass CUDA tensors)")
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unfor_compare")
-        n = _blocks(src.n, packed_len(ty, width), "unfor_compare input")
-        if n is None:
-            n = n_blocks if n_blocks is not None else (output.numel() // 32 if output is not None else 0)
+        n = _uniform_blocks(src, width, "unfor_compare", n_blocks, (output, 32))
         out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare")
         aux, stride, _ = FoR._ref(src, ty, reference, n)
-        k = _lib.CTYPE[ty](int(constant) & ((1 << _lib.BITS[ty]) - 1))
-        with torch.cuda.device(src.x.device):
-            _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare")(width, src.ptr, aux.ptr, stride, BitPacking.CMP[op], k, n,
-                                                                  out.data_ptr(), _stream(src)),
-                   f"fl_{ty}_unfor_compare")
+        _launch(f"fl_{ty}_unfor_compare", src.x.device, width, src.ptr, aux.ptr, stride, BitPacking.CMP[op], _scalar(ty, constant), n,
+                out.data_ptr())
         return out
 
     @staticmethod
@@ -430,21 +453,12 @@ class FoR:
         ty = src.ty
         if not src.torch:
             raise TypeError("unfor_compare_range is device tier (pass CUDA tensors)")
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unfor_compare_range")
-        n = _blocks(src.n, packed_len(ty, width), "unfor_compare_range input")
-        if n is None:
-            n = n_blocks if n_blocks is not None else (mask.numel() // 32 if _is_torch(mask) and cb else
-                                                       (output.numel() // 32 if output is not None else 0))
+        n = _uniform_blocks(src, width, "unfor_compare_range", n_blocks, (mask if cb and _is_torch(mask) else None, 32), (output, 32))
         m = _select_mask(src, mask, n) if cb else None
         out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_range")
         aux, stride, _ = FoR._ref(src, ty, reference, n)
-        M = (1 << _lib.BITS[ty]) - 1
-        with torch.cuda.device(src.x.device):
-            _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare_range")(width, src.ptr, aux.ptr, stride, _lib.CTYPE[ty](int(lo) & M),
-                                                                        _lib.CTYPE[ty](int(hi) & M), cb, m.ptr if m is not None and n else None,
-                                                                        n, out.data_ptr(), _stream(src)),
-                   f"fl_{ty}_unfor_compare_range")
+        _launch(f"fl_{ty}_unfor_compare_range", src.x.device, width, src.ptr, aux.ptr, stride, _scalar(ty, lo), _scalar(ty, hi), cb,
+                m.ptr if m is not None and n else None, n, out.data_ptr())
         return out
 
     @staticmethod
@@ -460,14 +474,9 @@ class FoR:
         ty = src.ty
         if not src.torch:
             raise TypeError("unfor_select is device tier (pass CUDA tensors)")
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unfor_select")
-        n = _blocks(src.n, packed_len(ty, width), "unfor_select input")
-        if n is None:
-            n = n_blocks if n_blocks is not None else (mask.numel() // 32 if _is_torch(mask) else 0)
+        n = _uniform_blocks(src, width, "unfor_select", n_blocks, (mask if _is_torch(mask) else None, 32))
         aux, stride, _ = FoR._ref(src, ty, reference, n)
-        return _select_call(f"fl_{ty}_unfor_select", ty, src, n, mask, out_offsets, total, output, check,
-                            lambda tail: (width, src.ptr, aux.ptr, stride, *tail))
+        return _select_call(f"fl_{ty}_unfor_select", src, n, (width, src.ptr, aux.ptr, stride), mask, out_offsets, total, output, check)
 
     @staticmethod
     def unfor_aggregate(width, packed, reference, mask=None, n_blocks=None, block_aggs=None, check=True):
@@ -482,15 +491,9 @@ class FoR:
         ty = src.ty
         if not src.torch:
             raise TypeError("unfor_aggregate is device tier (pass CUDA tensors)")
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_unfor_aggregate")
-        n = _blocks(src.n, packed_len(ty, width), "unfor_aggregate input")
-        if n is None:
-            n = n_blocks if n_blocks is not None else (mask.numel() // 32 if _is_torch(mask) else 0)
+        n = _uniform_blocks(src, width, "unfor_aggregate", n_blocks, (mask if _is_torch(mask) else None, 32))
         aux, stride, _ = FoR._ref(src, ty, reference, n)
-        return _aggregate_call(f"fl_{ty}_unfor_aggregate", src, n, mask, block_aggs, check,
-                               lambda tail: (width, src.ptr, aux.ptr, stride, *tail))
-
+        return _aggregate_call(f"fl_{ty}_unfor_aggregate", src, n, (width, src.ptr, aux.ptr, stride), mask, block_aggs, check)
 
 
 class Delta:
@@ -500,9 +503,9 @@ class Delta:
     def _go(method, width, input, base, output, per_block, n_blocks=None):
         src = _Arg(input)
         ty = src.ty
-        if width is not None and width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_{method}")
-        n = _blocks(src.n, per_block(ty), f"{method} input")
+        if width is not None:
+            _check_width(ty, width, method)
+        n = _blocks(src.n, per_block(ty), method)
         b = _Arg(base, ty)
         if n is None:
             n = n_blocks if n_blocks is not None else b.n // (1024 // _lib.BITS[ty])
@@ -544,9 +547,8 @@ class Delta:
             raise TypeError("transpose_delta_pack is a device-tier extension (pass CUDA tensors)")
         src = _Arg(input)
         ty = src.ty
-        if width > _lib.BITS[ty]:
-            raise FastLanesError(1, f"fl_{ty}_transpose_delta_pack")
-        n = _blocks(src.n, 1024, "transpose_delta_pack input")
+        _check_width(ty, width, "transpose_delta_pack")
+        n = _blocks(src.n, 1024, "transpose_delta_pack")
         b = _Arg(base, ty)
         if b.n != n * (1024 // _lib.BITS[ty]):
             raise ValueError("base must hold LANES elements per block")
@@ -561,7 +563,7 @@ class Transpose:
     def _go(method, input, output):
         src = _Arg(input)
         ty = src.ty
-        n = _blocks(src.n, 1024, f"{method} input")
+        n = _blocks(src.n, 1024, method)
         out = _out(src, output, ty, n * 1024, method)
         return _run(method, ty, None, src, out, n)
 
@@ -597,11 +599,9 @@ def widths_to_offsets(ty, widths):
     dev = w.x.device
     offsets = torch.empty(w.n, dtype=torch.int64, device=dev)
     total = torch.zeros(1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.load().fl_widths_to_offsets(_lib.BITS[ty], w.ptr, w.n, offsets.data_ptr(), total.data_ptr(),
-                                                err.data_ptr(), _stream(w)), "fl_widths_to_offsets")
-    _check_flag(err, "fl_widths_to_offsets")                    # bitpacking.rs:93 unreachable!()
+    flag = _Flag(True, dev)
+    _launch("fl_widths_to_offsets", dev, _lib.BITS[ty], w.ptr, w.n, offsets.data_ptr(), total.data_ptr(), flag.ptr)
+    flag.raise_if_set("fl_widths_to_offsets")                   # bitpacking.rs:93 unreachable!()
     return offsets, total
 
 
@@ -609,31 +609,38 @@ def widths_to_offsets(ty, widths):
 _WIDTHS_DECODERS = ("unpack_widths", "unfor_pack_widths", "undelta_pack_widths", "undelta_pack_untranspose_widths")
 
 
-def _widths_call(method, ty, widths, offsets, packed, unpacked, check, aux=()):
-    """`aux`: the C arguments between the two sides -- (references pointer, stride) for FoR, (bases pointer,) for Delta."""
-    import torch
+_NO_REFERENCES = object()
+
+
+def _widths_column(method, packed, widths, offsets, *others, references=_NO_REFERENCES):
+    """What every entry point over a mixed-width column opens with: `widths` as u8 and `offsets` as u64 on `packed`'s tier and device
+    (`others`: further buffers of the call, checked first), device tier only, one offset per block, and -- for FoR's forms -- the
+    blocks' references.  Returns the block count and the leading C arguments (widths, offsets, packed, packed_bytes[, references,
+    reference_stride])."""
     w = _Arg(widths, "u8")
     o = _Arg(offsets, "u64")
-    _same_tier(packed, unpacked, w, o)
+    _same_tier(packed, *others, w, o)
     if not packed.torch:
         raise TypeError(f"{method} is device tier: widths, offsets and data must be CUDA tensors")
     n = w.n
     if o.n != n:
         raise ValueError("offsets must hold one entry per block")
+    refs = _block_references(packed, packed.ty, references, n)[1] if references is not _NO_REFERENCES else ()
+    pbytes = packed.n * (_lib.BITS[packed.ty] // 8)     # the kernel skips (and flags) any block that does not lie inside these bytes
+    return n, (w.ptr, o.ptr, packed.ptr, pbytes, *refs)
+
+
+def _widths_call(method, ty, widths, offsets, packed, unpacked, check, aux=()):
+    """`aux`: the C arguments between the two sides -- (references pointer, stride) for FoR, (bases pointer,) for Delta."""
+    n, (w, o, pk, pbytes) = _widths_column(method, packed, widths, offsets, unpacked)
     if unpacked.n != n * 1024:
         raise ValueError(f"{method}: the unpacked column must hold 1024 elements per block")
-    dev = packed.x.device
-    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-    pbytes = packed.n * (_lib.BITS[ty] // 8)     # the kernel skips (and flags) any block that does not lie inside these bytes
+    flag = _Flag(check, packed.x.device)
     # C ABI argument order is (widths, offsets, in, [aux], out, ..): packed, packed_bytes -> unpacked for the decoders, the reverse
     # for the encoders
-    args = (packed.ptr, pbytes, *aux, unpacked.ptr) if method in _WIDTHS_DECODERS else (unpacked.ptr, *aux, packed.ptr, pbytes)
-    with torch.cuda.device(dev):
-        _check(getattr(_lib.load(), f"fl_{ty}_{method}")(w.ptr, o.ptr, *args, n,
-                                                         err.data_ptr() if check else None, _stream(packed)),
-               f"fl_{ty}_{method}")
-    if check:
-        _check_flag(err, f"fl_{ty}_{method}")                   # bitpacking.rs:93,126 unreachable!(); :78-80,111-113
+    args = (pk, pbytes, *aux, unpacked.ptr) if method in _WIDTHS_DECODERS else (unpacked.ptr, *aux, pk, pbytes)
+    _launch(f"fl_{ty}_{method}", packed.x.device, w, o, *args, n, flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_{method}")                      # bitpacking.rs:93,126 unreachable!(); :78-80,111-113
 
 
 def _block_references(src, ty, references, n):
@@ -701,40 +708,19 @@ def unfor_compare_widths(widths, offsets, packed, references, op, constant, outp
     import torch
     src = _Arg(packed)
     ty = src.ty
-    w = _Arg(widths, "u8")
-    o = _Arg(offsets, "u64")
-    _same_tier(src, w, o)
-    if not src.torch:
-        raise TypeError("unfor_compare_widths is device tier: widths, offsets and data must be CUDA tensors")
-    n = w.n
-    if o.n != n:
-        raise ValueError("offsets must hold one entry per block")
+    n, lead = _widths_column("unfor_compare_widths", src, widths, offsets, references=references)
     if op not in BitPacking.CMP:
         raise ValueError(f"op must be one of {sorted(BitPacking.CMP)}")
-    r, (rptr, stride) = _block_references(src, ty, references, n)
     out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_widths")
-    dev = src.x.device
-    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
-    k = _lib.CTYPE[ty](int(constant) & ((1 << _lib.BITS[ty]) - 1))
-    with torch.cuda.device(dev):
-        _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare_widths")(w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, BitPacking.CMP[op], k,
-                                                                     n, out.data_ptr(), err.data_ptr() if check else None, _stream(src)),
-               f"fl_{ty}_unfor_compare_widths")
-    if check:
-        _check_flag(err, f"fl_{ty}_unfor_compare_widths")       # bitpacking.rs:93,126 unreachable!(); :111-113
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_compare_widths", src.x.device, *lead, BitPacking.CMP[op], _scalar(ty, constant), n, out.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_compare_widths")          # bitpacking.rs:93,126 unreachable!(); :111-113
     return out
 
 
 def _select_mask(src, mask, n):
     """The selection mask of a select call: a CUDA tensor of 32 four-byte integer words per block, on the column's device."""
-    m = _Arg(mask)
-    _same_tier(src, m)
-    if m.x.dtype.is_floating_point or m.x.element_size() != 4:
-        raise TypeError(f"mask must be an int32 / uint32 tensor (32 words per block), got {m.x.dtype}")
-    if m.n != 32 * n:
-        raise ValueError(f"mask holds {m.n} words, expected 32 per block = {32 * n}")
-    return m
+    return _block_words(mask, "mask", 32, 4, src, n)[0]
 
 
 def _range_combine(combine, mask):
@@ -798,29 +784,13 @@ def unfor_compare_range_widths(widths, offsets, packed, references, lo, hi, mask
         raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block = {32 * widths.numel()}")
     src = _Arg(packed)
     ty = src.ty
-    w = _Arg(widths, "u8")
-    o = _Arg(offsets, "u64")
-    _same_tier(src, w, o)
-    if not src.torch:
-        raise TypeError("unfor_compare_range_widths is device tier: widths, offsets and data must be CUDA tensors")
-    n = w.n
-    if o.n != n:
-        raise ValueError("offsets must hold one entry per block")
+    n, lead = _widths_column("unfor_compare_range_widths", src, widths, offsets, references=references)
     m = _select_mask(src, mask, n) if cb else None
-    r, (rptr, stride) = _block_references(src, ty, references, n)
     out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_range_widths")
-    dev = src.x.device
-    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
-    M = (1 << _lib.BITS[ty]) - 1
-    with torch.cuda.device(dev):
-        _check(getattr(_lib.load(), f"fl_{ty}_unfor_compare_range_widths")(w.ptr, o.ptr, src.ptr, pbytes, rptr, stride,
-                                                                           _lib.CTYPE[ty](int(lo) & M), _lib.CTYPE[ty](int(hi) & M), cb,
-                                                                           m.ptr if m is not None and n else None, n, out.data_ptr(),
-                                                                           err.data_ptr() if check else None, _stream(src)),
-               f"fl_{ty}_unfor_compare_range_widths")
-    if check:
-        _check_flag(err, f"fl_{ty}_unfor_compare_range_widths")   # bitpacking.rs:93,126 unreachable!(); :111-113
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_compare_range_widths", src.x.device, *lead, _scalar(ty, lo), _scalar(ty, hi), cb,
+            m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_compare_range_widths")    # bitpacking.rs:93,126 unreachable!(); :111-113
     return out
 
 
@@ -832,23 +802,17 @@ def mask_offsets(mask):
     import torch
     if not _is_torch(mask):
         raise TypeError("mask_offsets is device tier (pass a CUDA int32 tensor)")
-    m = _Arg(mask)
-    if m.x.dtype.is_floating_point or m.x.element_size() != 4:
-        raise TypeError(f"mask must be an int32 / uint32 tensor (32 words per block), got {m.x.dtype}")
-    if m.n % 32:
-        raise ValueError(f"mask holds {m.n} words, not a multiple of 32 (one block)")
+    m, n = _block_words(mask, "mask", 32, 4)
     dev = m.x.device
-    n = m.n // 32
     offsets = torch.empty(n, dtype=torch.int64, device=dev)
     total = torch.zeros(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.load().fl_mask_offsets(m.ptr, n, offsets.data_ptr(), total.data_ptr(), _stream(m)), "fl_mask_offsets")
+    _launch("fl_mask_offsets", dev, m.ptr, n, offsets.data_ptr(), total.data_ptr())
     return offsets, total
 
 
-def _select_call(name, ty, src, n, mask, out_offsets, total, output, check, args):
-    """The part the two select forms share: mask / out_offsets / output validation, the launch, the error flag.  `args(tail)`
-    puts the form's own leading C arguments in front of (mask, out_offsets, out, out_len, n_blocks, err_flag, stream)."""
+def _select_call(name, src, n, lead, mask, out_offsets, total, output, check):
+    """The part the two select forms share: mask / out_offsets / output validation, the launch, the error flag.  `lead`: the
+    form's own leading C arguments, in front of (mask, out_offsets, out, out_len, n_blocks, err_flag, stream)."""
     import torch
     m = _select_mask(src, mask, n)
     if out_offsets is None:
@@ -861,15 +825,13 @@ def _select_call(name, ty, src, n, mask, out_offsets, total, output, check, args
     if output is None:
         if total is None:
             raise ValueError("output=None needs `total` (mask_offsets' second result) to size the result")
-        out = _Arg(torch.empty(int(total.item()), dtype=src.x.dtype, device=dev), ty)       # the one sync
+        out = _Arg(torch.empty(int(total.item()), dtype=src.x.dtype, device=dev), src.ty)   # the one sync
     else:
-        out = _Arg(output, ty)
+        out = _Arg(output, src.ty)
         _same_tier(src, out)
-    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-    with torch.cuda.device(dev):
-        _check(getattr(_lib.load(), name)(*args((m.ptr, oo.ptr, out.ptr, out.n, n, err.data_ptr() if check else None, _stream(src)))), name)
-    if check:
-        _check_flag(err, name)              # a run outside `output`; the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113
+    flag = _Flag(check, dev)
+    _launch(name, dev, *lead, m.ptr, oo.ptr, out.ptr, out.n, n, flag.ptr)
+    flag.raise_if_set(name)                 # a run outside `output`; the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113
     return out.x
 
 
@@ -882,19 +844,8 @@ def unfor_select_widths(widths, offsets, packed, references, mask, out_offsets=N
     block that fails them, or whose run does not fit `output`, is skipped (its output slots are left as they were); `check=True`
     reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
     src = _Arg(packed)
-    ty = src.ty
-    w = _Arg(widths, "u8")
-    o = _Arg(offsets, "u64")
-    _same_tier(src, w, o)
-    if not src.torch:
-        raise TypeError("unfor_select_widths is device tier: widths, offsets and data must be CUDA tensors")
-    n = w.n
-    if o.n != n:
-        raise ValueError("offsets must hold one entry per block")
-    r, (rptr, stride) = _block_references(src, ty, references, n)
-    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
-    return _select_call(f"fl_{ty}_unfor_select_widths", ty, src, n, mask, out_offsets, total, output, check,
-                        lambda tail: (w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, *tail))
+    n, lead = _widths_column("unfor_select_widths", src, widths, offsets, references=references)
+    return _select_call(f"fl_{src.ty}_unfor_select_widths", src, n, lead, mask, out_offsets, total, output, check)
 
 
 def aggregate_reduce(block_aggs):
@@ -904,21 +855,15 @@ def aggregate_reduce(block_aggs):
     import torch
     if not _is_torch(block_aggs):
         raise TypeError("aggregate_reduce is device tier (pass a CUDA int64 tensor)")
-    g = _Arg(block_aggs)
-    if g.x.dtype.is_floating_point or g.x.element_size() != 8:
-        raise TypeError(f"block_aggs must be an int64 / uint64 tensor (4 words per block), got {g.x.dtype}")
-    if g.n % 4:
-        raise ValueError(f"block_aggs holds {g.n} words, not a multiple of 4 (one block)")
-    dev = g.x.device
-    result = torch.empty(4, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.load().fl_aggregate_reduce(g.ptr if g.n else None, g.n // 4, result.data_ptr(), _stream(g)), "fl_aggregate_reduce")
+    g, n = _block_words(block_aggs, "block_aggs", 4, 8)
+    result = torch.empty(4, dtype=torch.int64, device=g.x.device)
+    _launch("fl_aggregate_reduce", g.x.device, g.ptr if n else None, n, result.data_ptr())
     return result
 
 
-def _aggregate_call(name, src, n, mask, block_aggs, check, args):
-    """The part the two aggregate forms share: mask / block_aggs validation, the two launches, the error flag.  `args(tail)` puts the
-    form's own leading C arguments in front of (mask, n_blocks, block_aggs, err_flag, stream)."""
+def _aggregate_call(name, src, n, lead, mask, block_aggs, check):
+    """The part the two aggregate forms share: mask / block_aggs validation, the two launches, the error flag.  `lead`: the form's
+    own leading C arguments, in front of (mask, n_blocks, block_aggs, err_flag, stream)."""
     import torch
     m = _select_mask(src, mask, n) if mask is not None else None
     dev = src.x.device
@@ -926,13 +871,10 @@ def _aggregate_call(name, src, n, mask, block_aggs, check, args):
         slots = torch.empty((n, 4), dtype=torch.int64, device=dev)
     else:
         slots = _consumer_out(src, block_aggs, torch.int64, n * 4, name[name.index("unfor"):]).view(n, 4)
-    err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-    with torch.cuda.device(dev):
-        _check(getattr(_lib.load(), name)(*args((m.ptr if m is not None and n else None, n, slots.data_ptr() if n else None,
-                                                 err.data_ptr() if check else None, _stream(src)))), name)
-    result = aggregate_reduce(slots)
-    if check:
-        _check_flag(err, name)              # the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113
+    flag = _Flag(check, dev)
+    _launch(name, dev, *lead, m.ptr if m is not None and n else None, n, slots.data_ptr() if n else None, flag.ptr)
+    result = aggregate_reduce(slots)        # enqueued before the flag is read back: the sync below covers both launches
+    flag.raise_if_set(name)                 # the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113
     return result, slots
 
 
@@ -944,19 +886,8 @@ def unfor_aggregate_widths(widths, offsets, packed, references, mask=None, block
     skipped and ITS SLOT HOLDS THE IDENTITY (0, 0, 2^64 - 1, 0), so `result` combines the valid blocks; `check=True` reads the device
     error flag back (one sync) and raises, `check=False` stays asynchronous."""
     src = _Arg(packed)
-    ty = src.ty
-    w = _Arg(widths, "u8")
-    o = _Arg(offsets, "u64")
-    _same_tier(src, w, o)
-    if not src.torch:
-        raise TypeError("unfor_aggregate_widths is device tier: widths, offsets and data must be CUDA tensors")
-    n = w.n
-    if o.n != n:
-        raise ValueError("offsets must hold one entry per block")
-    r, (rptr, stride) = _block_references(src, ty, references, n)
-    pbytes = src.n * (_lib.BITS[ty] // 8)        # the kernel skips (and flags) any block that does not lie inside these bytes
-    return _aggregate_call(f"fl_{ty}_unfor_aggregate_widths", src, n, mask, block_aggs, check,
-                           lambda tail: (w.ptr, o.ptr, src.ptr, pbytes, rptr, stride, *tail))
+    n, lead = _widths_column("unfor_aggregate_widths", src, widths, offsets, references=references)
+    return _aggregate_call(f"fl_{src.ty}_unfor_aggregate_widths", src, n, lead, mask, block_aggs, check)
 
 
 def for_pack_widths(widths, offsets, input, references, output, check=True):
@@ -983,8 +914,7 @@ def for_widths(mins, maxs):
     if hi.n != lo.n:
         raise ValueError("mins and maxs must hold one entry per block")
     widths = torch.empty(lo.n, dtype=torch.uint8, device=lo.x.device)
-    with torch.cuda.device(lo.x.device):
-        _check(getattr(_lib.load(), f"fl_{ty}_for_widths")(lo.ptr, hi.ptr, lo.n, widths.data_ptr(), _stream(lo)), f"fl_{ty}_for_widths")
+    _launch(f"fl_{ty}_for_widths", lo.x.device, lo.ptr, hi.ptr, lo.n, widths.data_ptr())
     return widths
 
 
@@ -1016,26 +946,9 @@ def unpack_single_widths(widths, offsets, packed, index):
     """`T::unchecked_unpack_single(widths[b], &packed[offsets[b]..], i)` (bitpacking.rs:58,181-200) batched over a mixed-width
     column: `index` is a CUDA int64/uint64 tensor of column-global element indices (block*1024 + i); returns the values.
     An index past the column raises like the reference's assert (bitpacking.rs:152), a width > T like its unreachable!()."""
-    import torch
     src = _Arg(packed)
-    ty = src.ty
-    w = _Arg(widths, "u8")
-    o = _Arg(offsets, "u64")
-    _same_tier(src, w, o)
-    if not src.torch:
-        raise TypeError("unpack_single_widths is device tier: pass CUDA tensors")
-    if o.n != w.n:
-        raise ValueError("offsets must hold one entry per block")
-    idx = _indices(index, src)
-    out = torch.empty(idx.numel(), dtype=src.x.dtype, device=src.x.device)
-    err = torch.zeros(1, dtype=torch.int32, device=src.x.device)
-    with torch.cuda.device(src.x.device):
-        _check(getattr(_lib.load(), f"fl_{ty}_unpack_single_widths")(w.ptr, o.ptr, src.ptr, src.n * (_lib.BITS[ty] // 8), w.n,
-                                                                    idx.data_ptr(), idx.numel(), out.data_ptr(), err.data_ptr(),
-                                                                    _stream(src)),
-               f"fl_{ty}_unpack_single_widths")
-    _check_flag(err, f"fl_{ty}_unpack_single_widths")
-    return out
+    n, lead = _widths_column("unpack_single_widths", src, widths, offsets)
+    return _single_call(f"fl_{src.ty}_unpack_single_widths", src, index, *lead, n)
 
 
 class Batch:
@@ -1088,7 +1001,7 @@ class Batch:
         self.max_blocks = max(nb)
         self.d_refs = None
         if references is not None:
-            r = [int(x) & ((1 << T) - 1) for x in references]          # python ints: a u64 reference may exceed int64
+            r = [_scalar(self.ty, x).value for x in references]        # python ints: a u64 reference may exceed int64
             if len(r) != self.n:
                 raise ValueError("references must hold one entry per array")
             self.d_refs = up(np.array(r, dtype=np.uint64).astype(_NP_DTYPE[self.ty]).view(np.uint8), np.uint8)
@@ -1108,45 +1021,32 @@ class Batch:
             self._keep += (list(bases),)
             self.d_bases = up([a.ptr for a in args_b], np.int64)
 
-    def _run_delta(self, method, extra, check):
-        import torch
-        if self.d_bases is None:
-            raise ValueError("this batch was built without bases")
-        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
-        first, last = (self.d_packed, self.d_unpacked) if method == "undelta_pack_batch" else (self.d_unpacked, self.d_packed)
-        with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _check(getattr(_lib.load(), f"fl_{self.ty}_{method}")(first.data_ptr(), self.d_bases.data_ptr(), last.data_ptr(), self.d_widths.data_ptr(),
-                                                                  self.d_n_blocks.data_ptr(), self.n, self.max_blocks, *extra,
-                                                                  err.data_ptr() if check else None, st), f"fl_{self.ty}_{method}")
-        if check:
-            _check_flag(err, f"fl_{self.ty}_{method}")
+    def _run(self, method, first, second, check, delta=False, extra=()):
+        """One launch over the batch.  The C argument order is (in, [bases], out, widths, [references], n_blocks, n_arrays, max_blocks,
+        [extra], err_flag, stream): Delta's per-array bases sit between the two sides, FoR's references after the widths."""
+        if delta:
+            if self.d_bases is None:
+                raise ValueError("this batch was built without bases")
+            data = (first.data_ptr(), self.d_bases.data_ptr(), second.data_ptr(), self.d_widths.data_ptr())
+        elif self.d_refs is not None:
+            method = {"unpack_batch": "unfor_pack_batch", "pack_batch": "for_pack_batch"}[method]
+            data = (first.data_ptr(), second.data_ptr(), self.d_widths.data_ptr(), self.d_refs.data_ptr())
+        else:
+            data = (first.data_ptr(), second.data_ptr(), self.d_widths.data_ptr())
+        flag = _Flag(check, self.device)
+        _launch(f"fl_{self.ty}_{method}", self.device, *data, self.d_n_blocks.data_ptr(), self.n, self.max_blocks, *extra, flag.ptr)
+        flag.raise_if_set(f"fl_{self.ty}_{method}")
 
     def undelta_pack(self, untranspose=False, check=False):
         """Delta::undelta_pack::<widths[a]> (delta.rs:47-63) on every block of every array with its bases; the output is in
         transposed order like the reference's, or in ORIGINAL order with `untranspose=True` (the fused extension)."""
-        self._run_delta("undelta_pack_batch", (1 if untranspose else 0,), check)
+        self._run("undelta_pack_batch", self.d_packed, self.d_unpacked, check, delta=True, extra=(1 if untranspose else 0,))
         return self.unpacked
 
     def transpose_delta_pack(self, check=False):
         """The fused encode pack::<widths[a]>(delta(transpose(unpacked[a]), bases[a])) for every array."""
-        self._run_delta("transpose_delta_pack_batch", (), check)
+        self._run("transpose_delta_pack_batch", self.d_unpacked, self.d_packed, check, delta=True)
         return self.packed
-
-    def _run(self, method, first, second, check):
-        import torch
-        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
-        if self.d_refs is not None:
-            method = {"unpack_batch": "unfor_pack_batch", "pack_batch": "for_pack_batch"}[method]
-        with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            args = [first.data_ptr(), second.data_ptr(), self.d_widths.data_ptr()]
-            if self.d_refs is not None:
-                args.append(self.d_refs.data_ptr())
-            args += [self.d_n_blocks.data_ptr(), self.n, self.max_blocks, err.data_ptr() if check else None, st]
-            _check(getattr(_lib.load(), f"fl_{self.ty}_{method}")(*args), f"fl_{self.ty}_{method}")
-        if check:
-            _check_flag(err, f"fl_{self.ty}_{method}")
 
     def unpack(self, check=False):
         """packed[a] -> unpacked[a] for every array; returns the list of unpacked tensors."""
@@ -1177,9 +1077,7 @@ class MixedWidthPlan:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._plan = ctypes.c_void_p()
         lib = _lib.load()
-        with torch.cuda.device(self.device):
-            _check(lib.fl_mixed_plan_create(_lib.BITS[ty], w.ctypes.data, w.size, ctypes.byref(self._plan)),
-                   "fl_mixed_plan_create")
+        _launch("fl_mixed_plan_create", self.device, _lib.BITS[ty], w.ctypes.data, w.size, ctypes.byref(self._plan), stream=False)
         self.n_blocks = int(lib.fl_mixed_plan_n_blocks(self._plan))
         self.packed_bytes = int(lib.fl_mixed_plan_packed_bytes(self._plan))
 
@@ -1203,34 +1101,26 @@ class MixedWidthPlan:
             if not a.torch or a.x.device != self.device:
                 raise ValueError(f"this plan lives on {self.device}: pass CUDA tensors of that device")
 
-    def unpack(self, packed, output=None):
-        import torch
-        src = _Arg(packed, self.ty)
-        esz = _lib.BITS[self.ty] // 8
-        if src.n * esz != self.packed_bytes:
-            raise ValueError("packed column has the wrong size for this plan")
-        out = _Arg(output, self.ty) if output is not None else _Arg(
-            torch.empty(self.n_blocks * 1024, dtype=self._torch_dtype(), device=self.device), self.ty)
-        if out.n != self.n_blocks * 1024:
-            raise ValueError("Output buffer must be of size 1024 per block")
-        self._on_device(src, out)
-        with torch.cuda.device(self.device):
-            _check(getattr(_lib.load(), f"fl_{self.ty}_unpack_mixed")(self._plan, src.ptr, out.ptr, _stream(out)),
-                   f"fl_{self.ty}_unpack_mixed")
-        return out.x
-
-    def pack(self, input, output=None):
+    def _run(self, method, input, n_in, bad_in, output, n_out, bad_out):
+        """Either direction over the plan: `input` of exactly n_in elements into `output` (a fresh tensor if None) of exactly n_out."""
         import torch
         src = _Arg(input, self.ty)
-        esz = _lib.BITS[self.ty] // 8
-        if src.n != self.n_blocks * 1024:
-            raise ValueError("Input buffer must be of size 1024 per block")
-        out = _Arg(output, self.ty) if output is not None else _Arg(
-            torch.empty(self.packed_bytes // esz, dtype=self._torch_dtype(), device=self.device), self.ty)
-        if out.n * esz != self.packed_bytes:
-            raise ValueError("packed column has the wrong size for this plan")
+        if src.n != n_in:
+            raise ValueError(bad_in)
+        out = _Arg(output if output is not None else torch.empty(n_out, dtype=self._torch_dtype(), device=self.device), self.ty)
+        if out.n != n_out:
+            raise ValueError(bad_out)
         self._on_device(src, out)
-        with torch.cuda.device(self.device):
-            _check(getattr(_lib.load(), f"fl_{self.ty}_pack_mixed")(self._plan, src.ptr, out.ptr, _stream(src)),
-                   f"fl_{self.ty}_pack_mixed")
+        _launch(f"fl_{self.ty}_{method}", self.device, self._plan, src.ptr, out.ptr)
         return out.x
+
+    def _packed_len(self):
+        return self.packed_bytes // (_lib.BITS[self.ty] // 8)
+
+    def unpack(self, packed, output=None):
+        return self._run("unpack_mixed", packed, self._packed_len(), "packed column has the wrong size for this plan",
+                         output, self.n_blocks * 1024, "Output buffer must be of size 1024 per block")
+
+    def pack(self, input, output=None):
+        return self._run("pack_mixed", input, self.n_blocks * 1024, "Input buffer must be of size 1024 per block",
+                         output, self._packed_len(), "packed column has the wrong size for this plan")
