@@ -10,18 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TYS = {"u8": 8, "u16": 16, "u32": 32, "u64": 64}
-CT = {"u8": "uint8_t", "u16": "uint16_t", "u32": "uint32_t", "u64": "uint64_t"}
+from cpu_support import CT, ROOT, TYPE_BITS, build_shim, lib  # noqa: F401 (lib: fixture)
+
 IDENTITY = (0, 0, 2 ** 64 - 1, 0)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build_library()
-    import fastlanes_amd
-    return fastlanes_amd.load()
 
 
 def test_header_declares_and_library_exports_the_nine_symbols(lib):
@@ -29,10 +20,10 @@ def test_header_declares_and_library_exports_the_nine_symbols(lib):
     text = open(os.path.join(ROOT, "include", "fastlanes_amd.h")).read()
     body = text.split("#define FL_DECLARE_AGGREGATE(T, S)")[1].split("FL_DECLARE_AGGREGATE(uint8_t, u8)")[0]
     assert sorted(re.findall(r"fl_##S##_(\w+)\(", body)) == ["unfor_aggregate", "unfor_aggregate_widths"]
-    for ty in TYS:
+    for ty in TYPE_BITS:
         assert f"FL_DECLARE_AGGREGATE({CT[ty]}, {ty})" in text
     assert "FL_DECLARE_AGGREGATE_REDUCE(aggregate_reduce)" in text
-    want = [f"fl_{ty}_{m}" for ty in TYS for m in ("unfor_aggregate", "unfor_aggregate_widths")] + ["fl_aggregate_reduce"]
+    want = [f"fl_{ty}_{m}" for ty in TYPE_BITS for m in ("unfor_aggregate", "unfor_aggregate_widths")] + ["fl_aggregate_reduce"]
     assert len(want) == 9 and sorted(fastlanes_amd.aggregate_symbols()) == sorted(want)
     for other in (fastlanes_amd.exported_symbols(), fastlanes_amd.for_compare_symbols(), fastlanes_amd.select_symbols()):
         assert not set(want) & set(other)                                  # the pinned lists stay as they were
@@ -57,7 +48,7 @@ def test_argument_checks_need_no_gpu(lib):
     # (block_aggs, n, result, stream)
     assert red(None, 1, p, None) == 3 and red(p, 1, None, None) == 3 and red(None, 0, None, None) == 3   # the result is always written
     assert red(p + 8, 1, p, None) == 4 and red(p, 1, p + 8, None) == 4
-    for ty, T in TYS.items():
+    for ty, T in TYPE_BITS.items():
         f = getattr(lib, f"fl_{ty}_unfor_aggregate")
         g = getattr(lib, f"fl_{ty}_unfor_aggregate_widths")
         # (width, in, refs, stride, mask, n, block_aggs, err, stream)
@@ -129,12 +120,7 @@ extern "C" int agg_no_decode(unsigned count, unsigned w, uint64_t ref, uint64_t*
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    d = tmp_path_factory.mktemp("aggregate_map")
-    src, so = d / "shim.cpp", d / "libshim.so"
-    src.write_text(SHIM)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-shared", "-fPIC", "-I",
-                           os.path.join(ROOT, "fastlanes_amd", "csrc"), str(src), "-o", str(so)])
-    s = ctypes.CDLL(str(so))
+    s = build_shim(tmp_path_factory, "aggregate_map", SHIM)
     s.agg_fold.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     s.agg_fold.restype = None
     s.agg_no_decode.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint64, ctypes.c_void_p]

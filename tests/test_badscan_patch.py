@@ -4,7 +4,7 @@ import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 CSRC = os.path.join(ROOT, "fastlanes_amd", "csrc")
 
 

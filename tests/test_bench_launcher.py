@@ -10,7 +10,7 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 BENCH = os.path.join(ROOT, "bench.py")
 
 

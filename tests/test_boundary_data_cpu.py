@@ -6,9 +6,8 @@ import pytest
 
 import bitmodel
 import boundary_data as bd
+from gpu_support import TYS
 from oracle_lib import TYPES, packed_len, tbits
-
-TYS = ["u8", "u16", "u32", "u64"]
 
 
 @pytest.mark.parametrize("ty", TYS)

@@ -8,15 +8,7 @@ import re
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build_library()
-    import fastlanes_amd
-    return fastlanes_amd.load()
+from cpu_support import ROOT, lib  # noqa: F401 (lib: fixture)
 
 
 def _header_symbols():

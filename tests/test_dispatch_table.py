@@ -5,7 +5,7 @@ import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 TABLE = os.path.join(ROOT, "fastlanes_amd", "csrc", "fl_dispatch_table.inc")
 
 

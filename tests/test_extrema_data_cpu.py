@@ -6,9 +6,9 @@ import pytest
 
 import bitmodel
 import extrema_data as ed
+from gpu_support import TYS
 from oracle_lib import TYPES, tbits
 
-TYS = ["u8", "u16", "u32", "u64"]
 U = np.uint64
 
 

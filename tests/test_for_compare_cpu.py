@@ -5,23 +5,14 @@ for u16 / u32 / u64."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TYS = {"u8": 8, "u16": 16, "u32": 32, "u64": 64}
+from cpu_support import ROOT, TYPE_BITS, build_shim, lib  # noqa: F401 (lib: fixture)
+
 OPS = ("==", "!=", "<", "<=", ">", ">=")            # fl_cmp 0..5
 EACH, ALL, NONE = 0, 1, 2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build_library()
-    import fastlanes_amd
-    return fastlanes_amd.load()
 
 
 def test_header_declares_and_library_exports_both_forms(lib):
@@ -29,9 +20,9 @@ def test_header_declares_and_library_exports_both_forms(lib):
     text = open(os.path.join(ROOT, "include", "fastlanes_amd.h")).read()
     body = text.split("#define FL_DECLARE_FOR_COMPARE(T, S)")[1].split("FL_DECLARE_FOR_COMPARE(uint8_t, u8)")[0]
     assert sorted(re.findall(r"fl_##S##_(\w+)\(", body)) == ["unfor_compare", "unfor_compare_widths"]
-    for ty in TYS:
+    for ty in TYPE_BITS:
         assert f"FL_DECLARE_FOR_COMPARE({ {'u8': 'uint8_t', 'u16': 'uint16_t', 'u32': 'uint32_t', 'u64': 'uint64_t'}[ty]}, {ty})" in text
-    want = [f"fl_{ty}_{m}" for ty in TYS for m in ("unfor_compare", "unfor_compare_widths")]
+    want = [f"fl_{ty}_{m}" for ty in TYPE_BITS for m in ("unfor_compare", "unfor_compare_widths")]
     assert sorted(fastlanes_amd.for_compare_symbols()) == sorted(want)
     for s in want:
         assert hasattr(lib, s), s
@@ -41,7 +32,7 @@ def test_argument_checks_need_no_gpu(lib):
     """Every refusal happens before the launch (no call here reaches a kernel)."""
     buf = np.zeros(4096, dtype=np.uint64)
     p = buf.ctypes.data
-    for ty, T in TYS.items():
+    for ty, T in TYPE_BITS.items():
         f = getattr(lib, f"fl_{ty}_unfor_compare")
         g = getattr(lib, f"fl_{ty}_unfor_compare_widths")
         # empty column: nothing to do, whatever the pointers
@@ -94,12 +85,7 @@ extern "C" void for_compare_decide_n(unsigned type_bits, size_t n, const int* op
 
 @pytest.fixture(scope="module")
 def decide(tmp_path_factory):
-    d = tmp_path_factory.mktemp("for_decide")
-    src, so = d / "shim.cpp", d / "libshim.so"
-    src.write_text(SHIM)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-shared", "-fPIC", "-I",
-                           os.path.join(ROOT, "fastlanes_amd", "csrc"), str(src), "-o", str(so)])
-    shim = ctypes.CDLL(str(so))
+    shim = build_shim(tmp_path_factory, "for_decide", SHIM)
     P = ctypes.c_void_p
     shim.for_compare_decide_n.argtypes = [ctypes.c_uint, ctypes.c_size_t] + [P] * 7
     shim.for_compare_decide_n.restype = None
@@ -150,7 +136,7 @@ def test_decide_sampled(decide, ty):
     """Seeded samples of the wider types, with k in {0, M}, r near M and W in {0, T-1, T} always among them.  The truth of
     (f + r) <op> k over f in [0, 2^W - 1] changes only where (f + r) mod 2^T crosses k or wraps, so evaluating it at f = 0 and at
     those crossings decides `all` / `none` / `each` independently of the helper."""
-    T = TYS[ty]
+    T = TYPE_BITS[ty]
     M = (1 << T) - 1
     rng = np.random.default_rng(4242 + T)
     q = []

@@ -11,20 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TYS = {"u8": 8, "u16": 16, "u32": 32, "u64": 64}
-CT = {"u8": "uint8_t", "u16": "uint16_t", "u32": "uint32_t", "u64": "uint64_t"}
+from cpu_support import CT, ROOT, TYPE_BITS, build_shim, lib  # noqa: F401 (lib: fixture)
+
 OPS = ("==", "!=", "<", "<=", ">", ">=")            # fl_cmp 0..5
 EACH, ALL, NONE = 0, 1, 2
 NEW, AND, OR = 0, 1, 2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build_library()
-    import fastlanes_amd
-    return fastlanes_amd.load()
 
 
 def test_header_declares_and_library_exports_the_eight_symbols(lib):
@@ -32,10 +23,10 @@ def test_header_declares_and_library_exports_the_eight_symbols(lib):
     text = open(os.path.join(ROOT, "include", "fastlanes_amd.h")).read()
     body = text.split("#define FL_DECLARE_FOR_COMPARE_RANGE(T, S)")[1].split("FL_DECLARE_FOR_COMPARE_RANGE(uint8_t, u8)")[0]
     assert sorted(re.findall(r"fl_##S##_(\w+)\(", body)) == ["unfor_compare_range", "unfor_compare_range_widths"]
-    for ty in TYS:
+    for ty in TYPE_BITS:
         assert f"FL_DECLARE_FOR_COMPARE_RANGE({CT[ty]}, {ty})" in text
     assert "typedef enum fl_mask_combine { FL_MASK_NEW = 0, FL_MASK_AND = 1, FL_MASK_OR = 2 } fl_mask_combine;" in text
-    want = [f"fl_{ty}_{m}" for ty in TYS for m in ("unfor_compare_range", "unfor_compare_range_widths")]
+    want = [f"fl_{ty}_{m}" for ty in TYPE_BITS for m in ("unfor_compare_range", "unfor_compare_range_widths")]
     assert len(want) == 8 and sorted(fastlanes_amd.for_compare_range_symbols()) == sorted(want)
     for other in (fastlanes_amd.exported_symbols(), fastlanes_amd.for_compare_symbols(), fastlanes_amd.select_symbols(),
                   fastlanes_amd.aggregate_symbols()):
@@ -51,7 +42,7 @@ def test_argument_checks_need_no_gpu(lib):
     buf = np.zeros(4096, dtype=np.uint64)
     p = buf.ctypes.data
     assert p % 16 == 0
-    for ty, T in TYS.items():
+    for ty, T in TYPE_BITS.items():
         f = getattr(lib, f"fl_{ty}_unfor_compare_range")
         g = getattr(lib, f"fl_{ty}_unfor_compare_range_widths")
         # f(width, in, refs, stride, lo, hi, combine, mask_in, n, mask, stream)
@@ -208,12 +199,7 @@ extern "C" long for_range_u8_exhaustive(int* bad)
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    d = tmp_path_factory.mktemp("for_range_decide")
-    src, so = d / "shim.cpp", d / "libshim.so"
-    src.write_text(SHIM)
-    subprocess.check_call(["g++", "-std=c++17", "-O3", "-Wall", "-Wextra", "-shared", "-fPIC", "-I",
-                           os.path.join(ROOT, "fastlanes_amd", "csrc"), str(src), "-o", str(so)])
-    lib = ctypes.CDLL(str(so))
+    lib = build_shim(tmp_path_factory, "for_range_decide", SHIM, opt="-O3")
     P = ctypes.c_void_p
     lib.for_range_decide_n.argtypes = [ctypes.c_uint, ctypes.c_size_t] + [P] * 9
     lib.for_range_decide_n.restype = None
@@ -254,7 +240,7 @@ def test_range_decide_at_the_edges(shim, ty):
     interesting width.  Membership of (f + r) mod 2^T in the cyclic interval changes only where it crosses lo, passes hi or wraps, so
     evaluating the definition at f = 0, 2^W - 1 and on both sides of those crossings decides ALL / NONE / EACH independently of the
     helper."""
-    T = TYS[ty]
+    T = TYPE_BITS[ty]
     N = 1 << T
     M = N - 1
     rng = np.random.default_rng(5150 + T)
@@ -333,7 +319,7 @@ def test_predicate_interval_edge_constants(shim, ty):
     """the wider types at the edge constants, on the bit patterns around every edge, against Python's integers; and for unsigned the
     same set of satisfying values as for_compare_predicate gives unfor_compare"""
     import fastlanes_amd as fl
-    T = TYS[ty]
+    T = TYPE_BITS[ty]
     N = 1 << T
     H = N >> 1
     edges = sorted({x % N for e in (0, 1, H - 1, H, H + 1, N - 2, N - 1, 12345 % N, N - 77) for x in (e - 1, e, e + 1)})

@@ -8,121 +8,17 @@ import pytest
 
 from datagen import values
 from oracle_lib import TYPES, packed_len, tbits
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import (IDENTITY, POLICIES, SENTINEL, SIGNED, TDT, TYS, BackgroundLoad, combine, expected_blocks, mask_set, mask_words,
+                         mixed_column, sentinel_slots, to_dev, u64_of)
 
 pytestmark = pytest.mark.gpu
-
-TYS = ["u8", "u16", "u32", "u64"]
-TDT = {"u8": "uint8", "u16": "uint16", "u32": "uint32", "u64": "uint64"}
-SIGNED = {"u8": "uint8", "u16": "int16", "u32": "int32", "u64": "int64"}      # same-width dtypes torch converts
-POLICIES = [0, 1, 2, 2 + 256 * 4 + 65536 * 4 + (1 << 24), 2 + 256 * 6 + 65536 * 3]
-GUARD = 96
-U64_MAX = np.uint64(2 ** 64 - 1)
-IDENTITY = np.array([0, 0, 2 ** 64 - 1, 0], dtype=np.uint64)
-SENTINEL = np.array(0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        return torch.empty(0, dtype=getattr(torch, str(a.dtype)), device="cuda:0")
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
-
-
-def u64_of(t):
-    """a CUDA int64 tensor -> numpy uint64, same shape"""
-    return t.contiguous().cpu().numpy().view(np.uint64)
-
-
-def mask_words(bits):
-    """bool[n * 1024] -> the device mask: 32 int32 words per block, bit i of word i // 32, LSB first"""
-    return to_dev(np.packbits(bits, bitorder="little").view(np.int32))
-
-
-def mixed_column(ty, widths, seed):
-    """(device widths, device offsets, packed column, per-block (w, packed) for the oracle)"""
-    import torch
-    esz = tbits(ty) // 8
-    widths = widths.astype(np.uint8)
-    off = np.concatenate([[0], np.cumsum(widths.astype(np.int64) * 128)]) // esz
-    col = values(ty, int(off[-1]), seed)
-    dw = torch.from_numpy(widths).cuda()
-    doff = torch.from_numpy((off[:-1] * esz).astype(np.int64)).cuda()
-    return dw, doff, col, [(int(w), col[off[b]:off[b + 1]]) for b, w in enumerate(widths)]
-
-
-def mask_set(n, rng, full=True):
-    """name -> bool[n * 1024] (the set of test_gpu_select.py), plus None: no mask, every row"""
-    N = n * 1024
-    out = {"zeros": np.zeros(N, bool), "ones": np.ones(N, bool)}
-    for i in (0, 31, 32, 1022, 1023):
-        m = np.zeros(N, bool)
-        m[i::1024] = True
-        out[f"bit {i}"] = m
-    out["0xAAAAAAAA"] = np.arange(N) % 2 == 1
-    for name, d in (("1/1024", 1 / 1024), ("1 %", 0.01), ("50 %", 0.5)):
-        out[f"random {name}"] = rng.random(N) < d
-    out["alternate"] = np.repeat(np.arange(n) % 2 == 1, 1024)
-    last = np.zeros(N, bool)
-    last[-1024:] = rng.random(1024) < 0.3
-    out["last block only"] = last
-    if not full:
-        out = {k: out[k] for k in ("zeros", "ones", "bit 1023", "0xAAAAAAAA", "random 1 %", "random 50 %", "alternate", "last block only")}
-    out["no mask"] = None
-    return out
-
-
-def expected_blocks(vals, bits):
-    """The reference: values (numpy over the oracle) and the mask's bits -> uint64[n, 4] = count, wrapping sum, min, max per block"""
-    v = vals.reshape(-1, 1024).astype(np.uint64)
-    b = np.ones(v.shape, bool) if bits is None else bits.reshape(-1, 1024)
-    out = np.empty((v.shape[0], 4), dtype=np.uint64)
-    out[:, 0] = b.sum(axis=1)
-    out[:, 1] = np.where(b, v, np.uint64(0)).sum(axis=1, dtype=np.uint64)
-    out[:, 2] = np.where(b, v, U64_MAX).min(axis=1)
-    out[:, 3] = np.where(b, v, np.uint64(0)).max(axis=1)
-    return out
-
-
-def combine(slots):
-    if slots.shape[0] == 0:
-        return IDENTITY.copy()
-    return np.array([slots[:, 0].sum(dtype=np.uint64), slots[:, 1].sum(dtype=np.uint64), slots[:, 2].min(), slots[:, 3].max()], dtype=np.uint64)
 
 
 def decodes_something(bits, widths, n):
     """some block has a non-empty mask AND a non-zero width: the decode path cannot be skipped wholesale"""
     kept = np.ones(n, bool) if bits is None else bits.reshape(n, 1024).any(axis=1)
     return bool((kept & (np.asarray(widths) > 0)).any())
-
-
-def sentinel_slots(n):
-    """(the whole buffer, its first n slots as [n, 4]): sentinel-filled, GUARD slots behind"""
-    import torch
-    buf = to_dev(np.full((n + GUARD) * 4, SENTINEL, dtype=np.uint64).view(np.int64))
-    assert buf.dtype == torch.int64
-    return buf, buf[:n * 4].view(n, 4)
 
 
 def check_slots(buf, n, result, want, what):
@@ -143,7 +39,7 @@ def test_mixed_width_columns_every_mask(fl, oracle, ty):
     dw, doff, col, blocks = mixed_column(ty, widths, 16200 + T)
     dcol = to_dev(col)
     refs = values(ty, n, 16300 + T)
-    masks = mask_set(n, rng)
+    masks = mask_set(n, rng, with_none=True)
     for rname, r_host, dref in (("per block", refs, to_dev(refs)), ("broadcast", np.full(n, refs[3], dtype=refs.dtype), to_dev(refs[3:4]))):
         vals = np.concatenate([oracle.unfor_pack(ty, w, pk, r_host[b]) for b, (w, pk) in enumerate(blocks)])
         for name, bits in masks.items():
@@ -166,7 +62,7 @@ def test_uniform_width_form(fl, oracle, ty):
     T = tbits(ty)
     rng = np.random.default_rng(16400 + T)
     n = 61
-    masks = mask_set(n, rng)
+    masks = mask_set(n, rng, with_none=True)
     for w in sorted({0, 1, 3, T // 2, T - 1, T}):
         pk = values(ty, n * packed_len(ty, w), 16500 + 64 * T + w)
         refs = values(ty, n, 16600 + 64 * T + w)
@@ -306,7 +202,7 @@ def test_policies_windows_streams_and_empty_columns(fl, oracle, kernel_policy, t
     vals2 = oracle.batch("unfor_pack", ty, T // 2, pk2, aux=refs, n_blocks=n)
     dcol, drefs, dpk2 = to_dev(col), to_dev(refs), to_dev(pk2)
     s = torch.cuda.Stream()
-    for name, bits in mask_set(n, rng, full=False).items():
+    for name, bits in mask_set(n, rng, full=False, with_none=True).items():
         assert name == "zeros" or decodes_something(bits, widths, n)
         dm = None if bits is None else mask_words(bits)
         (buf1, slots1), (buf2, slots2) = sentinel_slots(n), sentinel_slots(n)
@@ -337,29 +233,6 @@ def test_policies_windows_streams_and_empty_columns(fl, oracle, kernel_policy, t
         assert np.array_equal(u64_of(slots), want) and np.array_equal(u64_of(result), combine(want)), (ty, policy, "width 0")
         result, slots = fl.FoR.unfor_aggregate(0, empty, drefs[:5], dm, n_blocks=5)
         assert np.array_equal(u64_of(slots), want) and np.array_equal(u64_of(result), combine(want)), (ty, policy, "uniform width 0")
-
-
-class BackgroundLoad:
-    """Keeps every CU busy on a SECOND stream while the kernels under test run on the current one (as tests/test_gpu_full_check.py): a
-    queue of large decode launches (u32 W=20, 2 M blocks, ~2 ms each) refilled before every call under test."""
-
-    def __init__(self, fl):
-        import torch
-        self.torch, self.fl = torch, fl
-        self.stream = torch.cuda.Stream()
-        n = 2_000_000
-        self.pk = torch.empty(n * 640, dtype=torch.uint32, device="cuda:0")
-        assert fl.load().fl_fill_random(self.pk.data_ptr(), self.pk.numel() * 4, 3, None) == 0
-        self.out = torch.empty(n * 1024, dtype=torch.uint32, device="cuda:0")
-        torch.cuda.synchronize()
-
-    def refill(self, launches=3):
-        with self.torch.cuda.stream(self.stream):
-            for _ in range(launches):
-                self.fl.BitPacking.unpack(20, self.pk, output=self.out)
-
-    def drain(self):
-        self.stream.synchronize()
 
 
 @pytest.mark.parametrize("ty", ["u32", "u8"])

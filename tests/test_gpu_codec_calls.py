@@ -9,6 +9,8 @@ import re
 
 import pytest
 
+from gpu_support import fl  # noqa: F401 (fixture)
+
 pytestmark = pytest.mark.gpu
 
 TYS = ["u8", "u64"]
@@ -64,15 +66,6 @@ class Recorder:
     def one(self, name, *args):
         calls = self.take()
         assert calls == [(name, args)], f"\n got  {calls}\n want {[(name, args)]}"
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
 
 
 @pytest.fixture

@@ -12,51 +12,15 @@ import pytest
 
 import boundary_data as bd
 from oracle_lib import TYPES, packed_len, tbits
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import POLICIES as FOR_POLICIES  # the five of test_gpu_for_compare.py::test_policies_streams_and_empty_columns
+from gpu_support import TYS, to_dev, want_mask
 
 pytestmark = pytest.mark.gpu
 
-TYS = ["u8", "u16", "u32", "u64"]
 OPS = ["==", "!=", "<", "<=", ">", ">="]
-CMP = {"==": np.equal, "!=": np.not_equal, "<": np.less, "<=": np.less_equal, ">": np.greater, ">=": np.greater_equal}
 UNPACK_POLICIES = [0, 1, 2]
-# the five of test_gpu_for_compare.py::test_policies_streams_and_empty_columns
-FOR_POLICIES = [0, 1, 2, 2 + 256 * 4 + 65536 * 4 + (1 << 24), 2 + 256 * 6 + 65536 * 3]
 ONE_BLOCK_WIDTHS = (0, 7, 17)          # and W = T: the widths test_unpack_compare_u32_u64_every_width runs at one block too
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        return torch.empty(0, dtype=getattr(torch, str(a.dtype)), device="cuda:0")
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
-
-
-def want_mask(vals, op, k):
-    """numpy's mask of the values: 32 int32 words per 1024-value block, bit i of word i // 32, LSB first (as test_gpu_for_compare.py)."""
-    hit = CMP[op](vals, np.array(k, dtype=np.uint64).astype(vals.dtype))
-    return np.packbits(hit, bitorder="little").view(np.int32)
 
 
 def first_difference(got, want, T):

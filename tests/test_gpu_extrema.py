@@ -13,34 +13,13 @@ import pytest
 
 import extrema_data as ed
 from oracle_lib import TYPES, tbits
-from test_gpu_aggregate import GUARD, IDENTITY, POLICIES, SENTINEL, combine, expected_blocks, mask_words, sentinel_slots, to_dev, u64_of
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import GUARD, IDENTITY, POLICIES, SENTINEL, TYS, combine, expected_blocks, mask_words, sentinel_slots, to_dev, to_np, u64_of
 
 pytestmark = pytest.mark.gpu
 
-TYS = ["u8", "u16", "u32", "u64"]
 SLOTS = ("count", "sum", "min", "max")
 U = np.uint64
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
 
 
 @pytest.fixture
@@ -61,11 +40,6 @@ def column(oracle):
     get.clear = built.clear
     yield get
     built.clear()
-
-
-def to_np(t, ty):
-    import torch
-    return t.contiguous().view(torch.uint8).cpu().numpy().view(TYPES[ty][0])
 
 
 def place(T, pos):

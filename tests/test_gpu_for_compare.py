@@ -5,70 +5,12 @@ import pytest
 
 from datagen import values
 from oracle_lib import TYPES, packed_len, tbits
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import TDT, TYS, got_mask, mixed_column, to_dev, to_np, want_mask
 
 pytestmark = pytest.mark.gpu
 
-TYS = ["u8", "u16", "u32", "u64"]
 OPS = ["==", "!=", "<", "<=", ">", ">="]
-CMP = {"==": np.equal, "!=": np.not_equal, "<": np.less, "<=": np.less_equal, ">": np.greater, ">=": np.greater_equal}
-TDT = {"u8": "uint8", "u16": "uint16", "u32": "uint32", "u64": "uint64"}
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        return torch.empty(0, dtype=getattr(torch, str(a.dtype)), device="cuda:0")
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
-
-
-def to_np(t, ty):
-    import torch
-    return t.view(torch.uint8).cpu().numpy().view(TYPES[ty][0])
-
-
-def want_mask(vals, op, k):
-    """numpy's mask of unpacked values: 32 int32 words per 1024-value block, bit i of word i // 32, LSB first."""
-    hit = CMP[op](vals, np.array(k, dtype=np.uint64).astype(vals.dtype))
-    return np.packbits(hit, bitorder="little").view(np.int32)
-
-
-def got_mask(t):
-    return t.cpu().numpy().view(np.int32)
-
-
-def mixed_column(oracle, ty, widths, seed):
-    """(device widths, device offsets, packed column, per-block (w, packed) for the oracle)"""
-    import torch
-    T = tbits(ty)
-    esz = T // 8
-    widths = widths.astype(np.uint8)
-    off = np.concatenate([[0], np.cumsum(widths.astype(np.int64) * 128)]) // esz
-    col = values(ty, int(off[-1]), seed)
-    dw = torch.from_numpy(widths).cuda()
-    doff = torch.from_numpy((off[:-1] * esz).astype(np.int64)).cuda()
-    return dw, doff, col, [(int(w), col[off[b]:off[b + 1]]) for b, w in enumerate(widths)]
 
 
 def constants_for(ty, widths, refs, picks):
@@ -89,7 +31,7 @@ def test_mixed_width_columns_every_op(fl, oracle, ty):
     T = tbits(ty)
     rng = np.random.default_rng(9100 + T)
     for n, widths in ((T + 1, np.arange(T + 1)), (263, rng.integers(0, T + 1, size=263))):
-        dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9200 + n)
+        dw, doff, col, blocks = mixed_column(ty, widths, 9200 + n)
         dcol = to_dev(col)
         refs = values(ty, n, 9300 + n)
         for rname, r_host, dref in (("per block", refs, to_dev(refs)), ("broadcast", np.full(n, refs[3], dtype=refs.dtype), to_dev(refs[3:4]))):
@@ -166,7 +108,7 @@ def test_device_checks_match_unfor_pack_widths(fl, oracle, ty):
     n = 40
     rng = np.random.default_rng(9600 + T)
     widths = rng.integers(1, T + 1, size=n).astype(np.uint8)
-    dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9601)
+    dw, doff, col, blocks = mixed_column(ty, widths, 9601)
     refs = values(ty, n, 9602)
     vals = np.concatenate([oracle.unfor_pack(ty, w, pk, refs[b]) for b, (w, pk) in enumerate(blocks)])
     off = doff.cpu().numpy()
@@ -216,7 +158,7 @@ def test_policies_streams_and_empty_columns(fl, oracle, kernel_policy, ty, polic
     rng = np.random.default_rng(9700 + T)
     n = 131
     widths = rng.integers(0, T + 1, size=n)
-    dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9701)
+    dw, doff, col, blocks = mixed_column(ty, widths, 9701)
     refs = values(ty, n, 9702)
     vals = np.concatenate([oracle.unfor_pack(ty, w, pk, refs[b]) for b, (w, pk) in enumerate(blocks)])
     k = int(refs[n // 3])

@@ -7,48 +7,15 @@ import pytest
 
 from datagen import values
 from oracle_lib import TYPES, packed_len, tbits
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import TDT, TYS, got_mask, mixed_column, to_dev
 
 pytestmark = pytest.mark.gpu
 
-TYS = ["u8", "u16", "u32", "u64"]
 OPS = ["==", "!=", "<", "<=", ">", ">="]
 COMBINE = ["new", "and", "or"]
-TDT = {"u8": "uint8", "u16": "uint16", "u32": "uint32", "u64": "uint64"}
 EACH, ALL, NONE = 0, 1, 2
 PREFILL = 0x5A5A5A5A
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        return torch.empty(0, dtype=getattr(torch, str(a.dtype)), device="cuda:0")
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
-
-
-def got_mask(t):
-    return t.cpu().numpy().view(np.int32)
 
 
 def prefilled(n):
@@ -67,19 +34,6 @@ def want_mask(vals, lo, hi, combine="new", mask_in=None):
     """32 int32 words per 1024-value block, bit i of word i // 32, LSB first"""
     hit = np.packbits(hit_bits(vals, lo, hi), bitorder="little").view(np.int32)
     return hit if combine == "new" else (mask_in & hit) if combine == "and" else (mask_in | hit)
-
-
-def mixed_column(oracle, ty, widths, seed):
-    """(device widths, device offsets, packed column, per-block (w, packed) for the oracle)"""
-    import torch
-    T = tbits(ty)
-    esz = T // 8
-    widths = np.asarray(widths).astype(np.uint8)
-    off = np.concatenate([[0], np.cumsum(widths.astype(np.int64) * 128)]) // esz
-    col = values(ty, int(off[-1]), seed)
-    dw = torch.from_numpy(widths).cuda()
-    doff = torch.from_numpy((off[:-1] * esz).astype(np.int64)).cuda()
-    return dw, doff, col, [(int(w), col[off[b]:off[b + 1]]) for b, w in enumerate(widths)]
 
 
 # single-bit positions: the block's ends, the ends of the 16-byte slices lanes 0..7 load and store, and the first and last index of a
@@ -143,7 +97,7 @@ def test_mixed_width_columns_every_combiner(fl, oracle, ty):
     three_verdicts = {}
     for n, widths in ((T + 1, np.arange(T + 1)), (263, rng.integers(0, T + 1, size=263)), (1, [T // 2]), (2, [3, T]), (3, [T, 0, 1]),
                       (5, [2, T - 1, 0, T, 5])):
-        dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9200 + n)
+        dw, doff, col, blocks = mixed_column(ty, widths, 9200 + n)
         dcol = to_dev(col)
         refs = values(ty, n, 9300 + n)
         for rname, r_host, dref in (("per block", refs, to_dev(refs)), ("broadcast", np.full(n, refs[n // 2], dtype=refs.dtype), to_dev(refs[n // 2:n // 2 + 1]))):
@@ -219,7 +173,7 @@ def test_new_equals_unfor_compare_for_the_six_unsigned_ops(fl, oracle, ty):
     rng = np.random.default_rng(9700 + T)
     n = 70
     widths = rng.integers(0, T + 1, size=n)
-    dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9701)
+    dw, doff, col, blocks = mixed_column(ty, widths, 9701)
     refs = values(ty, n, 9702)
     dcol, drefs = to_dev(col), to_dev(refs)
     w = T // 2 + 1
@@ -249,7 +203,7 @@ def test_device_checks_match_unfor_compare_widths(fl, oracle, ty):
     n = 40
     rng = np.random.default_rng(9800 + T)
     widths = rng.integers(1, T + 1, size=n).astype(np.uint8)
-    dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9801)
+    dw, doff, col, blocks = mixed_column(ty, widths, 9801)
     refs = values(ty, n, 9802)
     vals = np.concatenate([oracle.unfor_pack(ty, w, pk, refs[b]) for b, (w, pk) in enumerate(blocks)])
     off = doff.cpu().numpy()
@@ -298,7 +252,7 @@ def test_policies_streams_and_empty_columns(fl, oracle, kernel_policy, ty, polic
     rng = np.random.default_rng(9900 + T)
     n = 131
     widths = rng.integers(0, T + 1, size=n)
-    dw, doff, col, blocks = mixed_column(oracle, ty, widths, 9901)
+    dw, doff, col, blocks = mixed_column(ty, widths, 9901)
     refs = values(ty, n, 9902)
     vals = np.concatenate([oracle.unfor_pack(ty, w, pk, refs[b]) for b, (w, pk) in enumerate(blocks)])
     r = int(refs[n // 3])
@@ -350,7 +304,7 @@ def test_signed_column_less_than_a_negative_constant(fl, oracle):
     n = 45
     widths = rng.integers(0, T + 1, size=n)
     widths[:7] = [0, 3, 3, 31, 32, 2, 0]
-    dw, doff, col, blocks = mixed_column(oracle, "u32", widths, 10001)
+    dw, doff, col, blocks = mixed_column("u32", widths, 10001)
     refs = values("u32", n, 10002)
     refs[:7] = [0xFFFFFFF0, 0xFFFFFFF8, 0x7FFFFFFC, 0x80000000, 5, 0xFFFFFFF8, 0x80000000]   # around -5, around the sign change, INT_MIN
     vals = np.concatenate([oracle.unfor_pack("u32", w, pk, refs[b]) for b, (w, pk) in enumerate(blocks)])

@@ -1,6 +1,6 @@
 """GPU: the tail and shape handling the four consumers of a FoR-packed column share (fl_for_block.hpp) -- unfor_compare,
 unfor_compare_range, unfor_select and unfor_aggregate on ONE small column per launch shape, each against numpy on the oracle's
-unfor_pack per block, through the helpers of the four kernels' own test files.
+unfor_pack per block, through tests/gpu_support.py and the helpers that belong to one kernel's own test file.
 
 The column has n = 2 * 4 * bpw + r blocks (a workgroup takes 4 * bpw): two full workgroups and a tail of r in {1, bpw - 1, bpw + 1}
 blocks -- shorter than bpw (the block-by-block route of select and aggregate, the short prefetched route of compare and range) or
@@ -13,16 +13,16 @@ import numpy as np
 import pytest
 
 import test_gpu_aggregate as agg
-import test_gpu_for_compare as cmp
 import test_gpu_for_compare_range as rng_
 import test_gpu_select as sel
 from datagen import values
 from oracle_lib import packed_len, tbits
-from test_gpu_for_compare_range import fl, kernel_policy, to_dev, got_mask, prefilled, PREFILL  # noqa: F401 (fixtures)
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import GUARD, IDENTITY, TYS, expected_blocks, got_mask, mixed_column, sentinel_buffer, sentinel_of, sentinel_slots, to_dev, want_mask
+from test_gpu_for_compare_range import PREFILL, prefilled
 
 pytestmark = pytest.mark.gpu
 
-TYS = ["u8", "u16", "u32", "u64"]
 # (kernel policy, blocks per wavefront the tails are cut for): the policies of test_gpu_for_compare_range.py; the default shapes take
 # at most 4 blocks per wavefront, policy 1 takes one
 SHAPES = [(0, 4), (1, 1), (2, 4), (2 + 256 * 4 + 65536 * 4 + (1 << 24), 4), (2 + 256 * 6 + 65536 * 3, 3), (2 + 256 * 4 + 65536 * 12 + (1 << 24), 12)]
@@ -63,7 +63,7 @@ def test_tails_and_special_blocks_through_every_consumer(fl, oracle, kernel_poli
         rs = np.random.default_rng(20000 + 64 * T + n)
         widths = rs.integers(1, T + 1, size=n)
         widths[ZERO_W] = 0
-        dw, doff, col, blocks = rng_.mixed_column(oracle, ty, widths, 20100 + n)
+        dw, doff, col, blocks = mixed_column(ty, widths, 20100 + n)
         refs = values(ty, n, 20200 + n)
         vals = np.concatenate([oracle.unfor_pack(ty, w, pk, refs[b]) for b, (w, pk) in enumerate(blocks)])
         bad_w = widths.astype(np.uint8)
@@ -84,8 +84,8 @@ def test_tails_and_special_blocks_through_every_consumer(fl, oracle, kernel_poli
         # unfor_compare
         g, flag = raw_masks(fl, ty, "unfor_compare", dbw, doff, dcol, drefs, n, dict(args=(fl.BitPacking.CMP["<="], lo)))
         assert flag == 1, (what, "compare", flag)
-        assert (g[BAD_W] == PREFILL).all() and np.array_equal(g[ok], cmp.want_mask(vals, "<=", lo).reshape(n, 32)[ok]), (what, "compare")
-        assert np.array_equal(got_mask(fl.FoR.unfor_compare(wu, dpku, drefs, "<=", lo)), cmp.want_mask(valsu, "<=", lo)), (what, "compare, uniform")
+        assert (g[BAD_W] == PREFILL).all() and np.array_equal(g[ok], want_mask(vals, "<=", lo).reshape(n, 32)[ok]), (what, "compare")
+        assert np.array_equal(got_mask(fl.FoR.unfor_compare(wu, dpku, drefs, "<=", lo)), want_mask(valsu, "<=", lo)), (what, "compare, uniform")
 
         # unfor_compare_range: NEW, AND, OR out of place, AND in place
         for code, cb in enumerate(rng_.COMBINE):
@@ -108,21 +108,21 @@ def test_tails_and_special_blocks_through_every_consumer(fl, oracle, kernel_poli
         # unfor_select: the skipped block's run keeps the sentinel
         oo, total = fl.mask_offsets(dm)
         kept = int(bits.sum())
-        buf = sel.sentinel_buffer(ty, kept + sel.GUARD)
+        buf = sentinel_buffer(ty, kept + GUARD)
         assert sel.raw_select_widths(fl, ty, dbw, doff, dcol, drefs, dm, oo, buf, buf.numel()) == 1, (what, "select")
         want = vals.copy()
-        want[BAD_W * 1024:(BAD_W + 1) * 1024] = sel.sentinel_of(ty)
+        want[BAD_W * 1024:(BAD_W + 1) * 1024] = sentinel_of(ty)
         sel.check_select(ty, buf, total, want, bits, (what, "select"))
-        buf = sel.sentinel_buffer(ty, kept + sel.GUARD)
+        buf = sentinel_buffer(ty, kept + GUARD)
         fl.FoR.unfor_select(wu, dpku, drefs, dm, out_offsets=oo, total=total, n_blocks=n, output=buf)
         sel.check_select(ty, buf, total, valsu, bits, (what, "select, uniform"))
 
         # unfor_aggregate: the skipped block's slot holds the identity
-        sbuf, slots = agg.sentinel_slots(n)
+        sbuf, slots = sentinel_slots(n)
         assert agg.raw_aggregate_widths(fl, ty, dbw, doff, dcol, drefs, dm, slots) == 1, (what, "aggregate")
-        want = agg.expected_blocks(vals, bits)
-        want[BAD_W] = agg.IDENTITY
+        want = expected_blocks(vals, bits)
+        want[BAD_W] = IDENTITY
         agg.check_slots(sbuf, n, fl.aggregate_reduce(slots), want, (what, "aggregate"))
-        sbuf, slots = agg.sentinel_slots(n)
+        sbuf, slots = sentinel_slots(n)
         result, _ = fl.FoR.unfor_aggregate(wu, dpku, drefs, dm, n_blocks=n, block_aggs=slots)
-        agg.check_slots(sbuf, n, result, agg.expected_blocks(valsu, bits), (what, "aggregate, uniform"))
+        agg.check_slots(sbuf, n, result, expected_blocks(valsu, bits), (what, "aggregate, uniform"))

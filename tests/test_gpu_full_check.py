@@ -16,15 +16,16 @@ import numpy as np
 import pytest
 
 from datagen import values
+from cpu_support import ROOT
+from gpu_support import fl  # noqa: F401 (fixture)
+from gpu_support import TYS, BackgroundLoad, to_dev
 from oracle_lib import TYPES, lanes, packed_len, tbits
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TYS = ["u8", "u16", "u32", "u64"]
 OPS = {"unpack": 0, "pack": 1, "delta": 2, "undelta": 3, "undelta_pack": 4, "transpose": 5, "untranspose": 6,
        "undelta_pack_untranspose": 7, "transpose_delta_pack": 8, "block_sums": 9, "compare": 10, "min_max": 11}
-CMP = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
+CMP_CODE = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
 
 
 def build_checker():
@@ -52,7 +53,7 @@ class Checker:
         ptr = lambda t: None if t is None else t.data_ptr()
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         rc = self.lib.naive_check(tbits(ty), OPS[op], width, ptr(a), ptr(aux), aux_stride, ptr(got), ptr(got2), n_blocks,
-                                  self.counter.data_ptr(), CMP[cmp_op], int(cmp_k), ptr(widths), ptr(offsets), st)
+                                  self.counter.data_ptr(), CMP_CODE[cmp_op], int(cmp_k), ptr(widths), ptr(offsets), st)
         assert rc == 0, f"naive_check failed to launch: {rc}"
         return int(self.counter.item())
 
@@ -62,21 +63,6 @@ def checker():
     import torch
     assert torch.cuda.is_available(), "gpu tests need a GPU"
     return Checker()
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
 
 
 def corrupt(t, at):
@@ -150,30 +136,6 @@ def test_the_checker_itself_against_the_oracle(checker, oracle, ty):
                            for b, w in enumerate(widths)])
     assert checker.mismatches(ty, "undelta_pack", 0, dcol, to_dev(want), n, aux=to_dev(bases), widths=dw_, offsets=doff) == 0
     assert checker.mismatches(ty, "undelta_pack", 0, dcol, corrupt(to_dev(want), at), n, aux=to_dev(bases), widths=dw_, offsets=doff) == 1
-
-
-class BackgroundLoad:
-    """Keeps every CU busy on a SECOND stream while the kernels under test run on the current one: a queue of large decode
-    launches (u32 W=20, 2 M blocks = 13 GB of traffic, ~2 ms each) refilled before every call under test."""
-
-    def __init__(self, fl):
-        import torch
-        self.torch, self.fl = torch, fl
-        self.stream = torch.cuda.Stream()
-        n = 2_000_000
-        self.pk = torch.empty(n * 640, dtype=torch.uint32, device="cuda:0")
-        rc = fl.load().fl_fill_random(self.pk.data_ptr(), self.pk.numel() * 4, 3, None)
-        assert rc == 0, (rc, fl.load().fl_last_hip_error())
-        self.out = torch.empty(n * 1024, dtype=torch.uint32, device="cuda:0")
-        torch.cuda.synchronize()
-
-    def refill(self, launches=3):
-        with self.torch.cuda.stream(self.stream):
-            for _ in range(launches):
-                self.fl.BitPacking.unpack(20, self.pk, output=self.out)
-
-    def drain(self):
-        self.stream.synchronize()
 
 
 FULL_WIDTHS = {"u8": (3, 5, 8), "u16": (3, 9, 13), "u32": (7, 12, 20, 31), "u64": (4, 17, 40)}

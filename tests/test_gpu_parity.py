@@ -10,53 +10,18 @@ import pytest
 
 from datagen import sha, values
 from golden.make_golden import N_BLOCKS, case_inputs
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import TYS, to_dev, to_np
 from oracle_lib import TYPES, lanes, packed_len, tbits
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "golden.json")))
-TYS = ["u8", "u16", "u32", "u64"]
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        return torch.empty(0, dtype=getattr(torch, str(a.dtype)), device="cuda:0")
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
-
-
-def to_np(t, ty):
-    import torch
-    if t.numel() == 0:
-        return np.zeros(0, dtype=TYPES[ty][0])
-    return t.view(torch.uint8).cpu().numpy().view(TYPES[ty][0])
 
 
 # ---------------------------------------------------------------------------
 # every (T, W): all width-parameterised ops vs the oracle, ragged block count
 # ---------------------------------------------------------------------------
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards (0 automatic, 1 cell-column kernels, 2 wave-per-block)."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
-
-
 @pytest.mark.parametrize("policy", [0, 1, 2])
 @pytest.mark.parametrize("ty", TYS)
 def test_all_widths_vs_oracle(fl, oracle, kernel_policy, ty, policy):

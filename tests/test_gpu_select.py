@@ -6,94 +6,11 @@ import numpy as np
 import pytest
 
 from datagen import values
-from oracle_lib import TYPES, packed_len, tbits
+from oracle_lib import packed_len, tbits
+from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
+from gpu_support import GUARD, POLICIES, SIGNED, TDT, TYS, BackgroundLoad, mask_set, mask_words, mixed_column, sentinel_buffer, sentinel_of, to_dev, to_np
 
 pytestmark = pytest.mark.gpu
-
-TYS = ["u8", "u16", "u32", "u64"]
-TDT = {"u8": "uint8", "u16": "uint16", "u32": "uint32", "u64": "uint64"}
-SIGNED = {"u8": "uint8", "u16": "int16", "u32": "int32", "u64": "int64"}      # same-width dtypes torch compares / indexes
-POLICIES = [0, 1, 2, 2 + 256 * 4 + 65536 * 4 + (1 << 24), 2 + 256 * 6 + 65536 * 3]
-GUARD = 96
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
-
-
-@pytest.fixture
-def kernel_policy(fl):
-    """fl_internal_set_kernel_policy for one test, restored afterwards."""
-    lib = fl.load()
-
-    def set_policy(p):
-        lib.fl_internal_set_kernel_policy(p)
-        assert lib.fl_internal_get_kernel_policy() == p
-    yield set_policy
-    lib.fl_internal_set_kernel_policy(0)
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        return torch.empty(0, dtype=getattr(torch, str(a.dtype)), device="cuda:0")
-    return torch.from_numpy(a.view(np.uint8)).to("cuda:0").view(getattr(torch, str(a.dtype)))
-
-
-def to_np(t, ty):
-    import torch
-    return t.contiguous().view(torch.uint8).cpu().numpy().view(TYPES[ty][0])
-
-
-def mask_words(bits):
-    """bool[n * 1024] -> the device mask: 32 int32 words per block, bit i of word i // 32, LSB first"""
-    return to_dev(np.packbits(bits, bitorder="little").view(np.int32))
-
-
-def sentinel_of(ty):
-    return np.array(0xA5A5A5A5A5A5A5A5, dtype=np.uint64).astype(TYPES[ty][0])
-
-
-def sentinel_buffer(ty, n_elems):
-    return to_dev(np.full(n_elems, sentinel_of(ty), dtype=TYPES[ty][0]))
-
-
-def mixed_column(ty, widths, seed):
-    """(device widths, device offsets, packed column, per-block (w, packed) for the oracle)"""
-    import torch
-    esz = tbits(ty) // 8
-    widths = widths.astype(np.uint8)
-    off = np.concatenate([[0], np.cumsum(widths.astype(np.int64) * 128)]) // esz
-    col = values(ty, int(off[-1]), seed)
-    dw = torch.from_numpy(widths).cuda()
-    doff = torch.from_numpy((off[:-1] * esz).astype(np.int64)).cuda()
-    return dw, doff, col, [(int(w), col[off[b]:off[b + 1]]) for b, w in enumerate(widths)]
-
-
-def mask_set(n, rng, full=True):
-    """name -> bool[n * 1024]"""
-    N = n * 1024
-    out = {"zeros": np.zeros(N, bool), "ones": np.ones(N, bool)}
-    for i in (0, 31, 32, 1022, 1023):
-        m = np.zeros(N, bool)
-        m[i::1024] = True
-        out[f"bit {i}"] = m
-    out["0xAAAAAAAA"] = np.arange(N) % 2 == 1
-    for name, d in (("1/1024", 1 / 1024), ("1 %", 0.01), ("50 %", 0.5)):
-        out[f"random {name}"] = rng.random(N) < d
-    out["alternate"] = np.repeat(np.arange(n) % 2 == 1, 1024)
-    last = np.zeros(N, bool)
-    last[-1024:] = rng.random(1024) < 0.3
-    out["last block only"] = last
-    if not full:
-        out = {k: out[k] for k in ("zeros", "ones", "bit 1023", "0xAAAAAAAA", "random 1 %", "random 50 %", "alternate", "last block only")}
-    return out
 
 
 def check_select(ty, got_buf, total_dev, vals, bits, what):
@@ -325,29 +242,6 @@ def test_policies_windows_streams_and_empty_columns(fl, oracle, kernel_policy, t
     assert np.array_equal(to_np(got, ty), np.repeat(refs[:5], 1024)[bits]), (ty, policy, "width 0")
     got = fl.FoR.unfor_select(0, empty, drefs[:5], mask_words(bits), n_blocks=5)
     assert np.array_equal(to_np(got, ty), np.repeat(refs[:5], 1024)[bits]), (ty, policy, "uniform width 0")
-
-
-class BackgroundLoad:
-    """Keeps every CU busy on a SECOND stream while the kernels under test run on the current one (as tests/test_gpu_full_check.py): a
-    queue of large decode launches (u32 W=20, 2 M blocks, ~2 ms each) refilled before every call under test."""
-
-    def __init__(self, fl):
-        import torch
-        self.torch, self.fl = torch, fl
-        self.stream = torch.cuda.Stream()
-        n = 2_000_000
-        self.pk = torch.empty(n * 640, dtype=torch.uint32, device="cuda:0")
-        assert fl.load().fl_fill_random(self.pk.data_ptr(), self.pk.numel() * 4, 3, None) == 0
-        self.out = torch.empty(n * 1024, dtype=torch.uint32, device="cuda:0")
-        torch.cuda.synchronize()
-
-    def refill(self, launches=3):
-        with self.torch.cuda.stream(self.stream):
-            for _ in range(launches):
-                self.fl.BitPacking.unpack(20, self.pk, output=self.out)
-
-    def drain(self):
-        self.stream.synchronize()
 
 
 @pytest.mark.parametrize("ty", ["u32", "u8"])

@@ -4,21 +4,13 @@ chunk, and larger columns use its offsets on both sides of the comparison."""
 import numpy as np
 import pytest
 
+from gpu_support import fl  # noqa: F401 (fixture)
+from gpu_support import TYS
 from oracle_lib import tbits
 
 pytestmark = pytest.mark.gpu
 
-TYS = ["u8", "u16", "u32", "u64"]
 COUNTS = [1, 4095, 4096, 4097, 8191, 8192, 8193, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, (1 << 21) + 5]
-
-
-@pytest.fixture(scope="module")
-def fl():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import fastlanes_amd
-    fastlanes_amd.load()  # fails loudly if the HIP extension is missing
-    return fastlanes_amd
 
 
 def offsets_of(fl, ty, widths):

@@ -4,7 +4,7 @@ sanitizers instead)."""
 import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 
 
 def test_oracle_under_asan_ubsan(tmp_path):

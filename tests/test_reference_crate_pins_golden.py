@@ -15,7 +15,7 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 CRATE = os.path.join(ROOT, "bindings", "rust", "golden_dump")
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "golden.json")))
 

@@ -14,7 +14,7 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 HEADER = os.path.join(ROOT, "include", "fastlanes_amd.h")
 RUST = os.path.join(ROOT, "bindings", "rust", "src")
 

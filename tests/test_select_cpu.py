@@ -5,22 +5,11 @@ exactly once and lands every kept element where np.flatnonzero puts it."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TYS = {"u8": 8, "u16": 16, "u32": 32, "u64": 64}
-CT = {"u8": "uint8_t", "u16": "uint16_t", "u32": "uint32_t", "u64": "uint64_t"}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build_library()
-    import fastlanes_amd
-    return fastlanes_amd.load()
+from cpu_support import CT, ROOT, TYPE_BITS, build_shim, lib  # noqa: F401 (lib: fixture)
 
 
 def test_header_declares_and_library_exports_the_nine_symbols(lib):
@@ -28,10 +17,10 @@ def test_header_declares_and_library_exports_the_nine_symbols(lib):
     text = open(os.path.join(ROOT, "include", "fastlanes_amd.h")).read()
     body = text.split("#define FL_DECLARE_SELECT(T, S)")[1].split("FL_DECLARE_SELECT(uint8_t, u8)")[0]
     assert sorted(re.findall(r"fl_##S##_(\w+)\(", body)) == ["unfor_select", "unfor_select_widths"]
-    for ty in TYS:
+    for ty in TYPE_BITS:
         assert f"FL_DECLARE_SELECT({CT[ty]}, {ty})" in text
     assert "FL_DECLARE_MASK_OFFSETS(mask_offsets)" in text
-    want = ["fl_mask_offsets"] + [f"fl_{ty}_{m}" for ty in TYS for m in ("unfor_select", "unfor_select_widths")]
+    want = ["fl_mask_offsets"] + [f"fl_{ty}_{m}" for ty in TYPE_BITS for m in ("unfor_select", "unfor_select_widths")]
     assert len(want) == 9 and sorted(fastlanes_amd.select_symbols()) == sorted(want)
     assert not set(want) & set(fastlanes_amd.exported_symbols())          # the pinned list stays as it was
     for s in want:
@@ -47,7 +36,7 @@ def test_argument_checks_need_no_gpu(lib):
     assert mo(None, 0, None, None, None) == 0                              # empty column
     assert mo(None, 1, p, None, None) == 3 and mo(p, 1, None, None, None) == 3
     assert mo(p + 4, 1, p, None, None) == 4
-    for ty, T in TYS.items():
+    for ty, T in TYPE_BITS.items():
         f = getattr(lib, f"fl_{ty}_unfor_select")
         g = getattr(lib, f"fl_{ty}_unfor_select_widths")
         # (width, in, refs, stride, mask, out_offsets, out, out_len, n, err, stream)
@@ -153,12 +142,7 @@ extern "C" int select_map_block(unsigned sz, const uint32_t* mask, int* owner, i
 
 @pytest.fixture(scope="module")
 def select_map(tmp_path_factory):
-    d = tmp_path_factory.mktemp("select_map")
-    src, so = d / "shim.cpp", d / "libshim.so"
-    src.write_text(SHIM)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-shared", "-fPIC", "-I",
-                           os.path.join(ROOT, "fastlanes_amd", "csrc"), str(src), "-o", str(so)])
-    shim = ctypes.CDLL(str(so))
+    shim = build_shim(tmp_path_factory, "select_map", SHIM)
     shim.select_map_block.argtypes = [ctypes.c_uint] + [ctypes.c_void_p] * 4
     shim.select_map_block.restype = ctypes.c_int
 
@@ -171,9 +155,9 @@ def select_map(tmp_path_factory):
     return run
 
 
-@pytest.mark.parametrize("ty", list(TYS))
+@pytest.mark.parametrize("ty", list(TYPE_BITS))
 def test_select_map_tiles_the_mask_and_lands_in_index_order(select_map, ty):
-    sz = TYS[ty] // 8
+    sz = TYPE_BITS[ty] // 8
     rng = np.random.default_rng(1400 + sz)
     masks = [np.zeros(1024, bool), np.ones(1024, bool), np.arange(1024) % 2 == 1]
     for i in (0, 31, 32, 1022, 1023):

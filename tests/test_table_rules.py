@@ -4,7 +4,7 @@ runs whose right answer is obvious -- the committed tables are checked against t
 import importlib.util
 import os
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 
 
 def _load(name):

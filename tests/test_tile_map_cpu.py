@@ -5,12 +5,12 @@ bytes are written twice), a tile missed at an untested block count is invisible 
 to hand each XCD (workgroup id mod 8) one contiguous run of every window."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT, build_shim
+
 ROTATE = 0x80
 SHIFTS = list(range(14)) + [16, 20, 31, 32, 63]
 
@@ -85,12 +85,7 @@ unsigned plan(uint64_t n_tiles, unsigned ws, uint64_t* tpx, unsigned* ws_out)
 
 @pytest.fixture(scope="module")
 def tm(tmp_path_factory):
-    d = tmp_path_factory.mktemp("tile_map")
-    src, so = d / "shim.cpp", d / "libshim.so"
-    src.write_text(SHIM)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-shared", "-fPIC", "-pthread", "-I",
-                           os.path.join(ROOT, "fastlanes_amd", "csrc"), str(src), "-o", str(so)])
-    lib = ctypes.CDLL(str(so))
+    lib = build_shim(tmp_path_factory, "tile_map", SHIM, extra=("-pthread",))
     for u in ("u64", "u32"):
         getattr(lib, "tiles_" + u).argtypes = [ctypes.c_uint, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]
         getattr(lib, "tiles_" + u).restype = None

@@ -5,7 +5,7 @@ import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpu_support import ROOT
 TABLE = os.path.join(ROOT, "fastlanes_amd", "csrc", "fl_window_table.inc")
 OPS = ["UNPACK", "PACK", "UNDELTA_PACK", "UNDELTA_PACK_UNTRANSPOSE", "TRANSPOSE_DELTA_PACK", "DELTA", "UNDELTA", "TRANSPOSE", "UNTRANSPOSE",
        "UNPACK_COMPARE", "UNPACK_BLOCK_SUMS", "BLOCK_MIN_MAX"]
