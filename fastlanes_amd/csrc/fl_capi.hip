@@ -2,7 +2,9 @@
 // Validates arguments, maps the runtime width to the per-(T,W) kernel instance
 // (the reference's `match width`, bitpacking.rs:82-95) and launches it.  No CPU
 // compute path exists in this library: every entry point ends in a HIP launch.
-// fl_column_pair_alloc / _free and the memory-class probe live in fl_pair.hip.
+// In this order: the kernel policy; the builders of the launch-argument blocks and the device tier's validators (run_* / dev_*);
+// fl_mixed_plan; extern "C" -- the public entry points, then the fl_internal_* ones of the A/B tools.  The host tier (HostCtx, host_run)
+// is fl_host_tier.hpp, part of this translation unit; fl_column_pair_alloc / _free and the memory-class probe live in fl_pair.hip.
 #include "../../include/fastlanes_amd.h"
 #include "../../include/fastlanes_amd_internal.h"
 #include "fl_host.hpp"
@@ -18,11 +20,10 @@
 #include "fl_for_compare_range.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
+#include "fl_host_tier.hpp"
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <cstring>
 #include <new>
 
 namespace {
@@ -37,15 +38,13 @@ std::atomic<int> g_kernel_policy{0};
 struct KernelPolicy {
     int mode;
     int waves;            // 0 = the launch's own
-    unsigned bpw;         // 0 = the launch's own blocks per wavefront and prefetch
-    unsigned prefetch;
+    int bpw;              // 0 = the launch's own blocks per wavefront and prefetch
+    int prefetch;
+    int window;           // 0 = the window table's
 };
-inline KernelPolicy kernel_policy()
-{
-    const int p = g_kernel_policy.load(std::memory_order_relaxed);
-    const bool ab = (p & 0xff) == 2;
-    return {p & 0xff, ab ? (p >> 8) & 0xff : 0, ab ? (unsigned)(p >> 16) & 0xffu : 0u, (unsigned)(p >> 24) & 1u};
-}
+// THE bit layout.  Only what fl_internal_set_kernel_policy accepted is ever stored, so waves and bpw are 0 outside mode 2.
+inline KernelPolicy policy_fields(int p) { return {p & 0xff, (p >> 8) & 0xff, (p >> 16) & 0xff, (p >> 24) & 1, (p >> 25) & 31}; }
+inline KernelPolicy kernel_policy() { return policy_fields(g_kernel_policy.load(std::memory_order_relaxed)); }
 
 // The shape of a wave-per-block launch: waves per SIMD, blocks per wavefront, prefetch (fl_widths.hpp).  Each family's default comes
 // from fl_dispatch.hpp; with_policy lays the A/B tools' overrides over it (the launcher tidies bpw / prefetch: tidy_wave_blocks).
@@ -57,7 +56,7 @@ inline WaveShape with_policy(WaveShape sh)
 {
     const KernelPolicy p = kernel_policy();
     if (p.waves) sh.waves = p.waves;
-    if (p.bpw) { sh.bpw = p.bpw; sh.prefetch = p.prefetch; }
+    if (p.bpw) { sh.bpw = (unsigned)p.bpw; sh.prefetch = (unsigned)p.prefetch; }
     return sh;
 }
 
@@ -75,6 +74,55 @@ inline WaveChoice chosen_waves(unsigned type_bits, unsigned w, fl::WaveOp op)
     WaveChoice c = p.waves ? WaveChoice{p.waves, false} : table.waves ? table : WaveChoice{fl::wave_fallback(type_bits, pack), false};
     if (p.bpw) c.two_blocks = p.bpw == 2;         // the A/B tools force either form: 2 + 256 * waves + 65536 * {1, 2}
     return c;
+}
+
+// the A/B tools' op number (0 unpack, 1 pack, 2 undelta_pack, 3 unpack over a mixed-width column) as the tables know it
+struct ToolOp {
+    WaveOp wave;
+    WindowOp window;
+};
+inline ToolOp tool_op(int op)
+{
+    return op == 1 ? ToolOp{WAVE_PACK, WIN_PACK} : op == 2 ? ToolOp{WAVE_UNDELTA_PACK, WIN_UNDELTA_PACK} : ToolOp{WAVE_UNPACK, WIN_UNPACK};
+}
+
+// 16 aligned zero bytes stand in for a buffer that has none: the packed side of a mixed-width column whose blocks all have width 0
+// (packed_bytes == 0, so any block with a width > 0 fails the kernel's bounds check), the output of a selection that keeps nothing
+template <typename T> const T* no_bytes()
+{
+    static const T zeros[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
+    return zeros;
+}
+
+// The packed column of a wave-per-block launch: blocks of one `width` back to back, or mixed (widths[] / offsets[] read and checked
+// per block by the kernel against packed_bytes).
+struct Column {
+    bool mixed;
+    unsigned width;
+    const uint8_t* widths = nullptr;
+    const uint64_t* offsets = nullptr;
+    size_t packed_bytes = 0;
+};
+// THE place that fills a WidthsArgs.  refs: FoR's references, null for plain BitPacking -- and for the four consumers, whose kernels
+// load the references with the block's metadata.  The callers differ in the wave shape, which they state.
+template <typename T>
+void widths_args(WidthsArgs& a, const Column& col, const void* packed, void* unpacked, const void* refs, size_t ref_stride,
+                 uint32_t* err_flag, size_t n_blocks, const WaveShape& sh)
+{
+    a.packed = static_cast<const char*>(packed);
+    a.unpacked = static_cast<char*>(unpacked);
+    a.widths = col.mixed ? col.widths : nullptr;
+    a.offsets = col.mixed ? col.offsets : nullptr;
+    a.err_flag = err_flag;
+    a.refs = refs;
+    a.ref_stride = ref_stride;
+    a.n_blocks = n_blocks;
+    a.uniform_width = col.mixed ? 0u : col.width;
+    a.packed_bytes = col.mixed ? col.packed_bytes : 0;          // uniform: not read, such calls are validated here, on the host side
+    a.bpw = sh.bpw;
+    a.prefetch = sh.prefetch;
+    a.linear_map = 0;                                           // the A/B tools' own launches set it, never the library's
+    a.nt_from = col.mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
 }
 
 template <typename T>
@@ -116,9 +164,8 @@ int run_chain(int op, int waves, unsigned w, const T* in, const T* bases, T* out
     const bool needs_bases = op != fl::OP_TRANSPOSE && op != fl::OP_UNTRANSPOSE;
     if (widths) {
         // a column whose blocks all have width 0 has no packed bytes: its packed pointer may be NULL (run_widths)
-        static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-        if (packed_bytes == 0 && packed_in && !in) in = no_bytes;
-        if (packed_bytes == 0 && packed_out && !out) out = const_cast<T*>(no_bytes);   // never written: every block is skipped or has W = 0
+        if (packed_bytes == 0 && packed_in && !in) in = no_bytes<T>();
+        if (packed_bytes == 0 && packed_out && !out) out = const_cast<T*>(no_bytes<T>());   // never written: every block is skipped or has W = 0
         if (!(packed_in || packed_out) || !offsets) return FL_ERR_NULL;
     }
     if ((!out && !(packed_out && w == 0 && !widths)) || (needs_bases && !bases) || (!(packed_in && w == 0 && !widths) && !in)) return FL_ERR_NULL;
@@ -137,6 +184,19 @@ int run_chain(int op, int waves, unsigned w, const T* in, const T* bases, T* out
     return hip_status(fn(a, waves, static_cast<hipStream_t>(stream)));
 }
 
+// run_chain where the policy chose the pipeline kernel (c.waves); where it did not, or the op has no pipeline form (-1: cannot happen
+// today), the cell-column kernel `cell`
+template <typename T>
+int run_chain_or_stream(int op, WaveChoice c, unsigned w, stream_launch_t cell, const T* in, const T* bases, T* out, size_t n,
+                        bool need_in, bool need_out, void* s)
+{
+    if (c.waves) {
+        const int rc = run_chain<T>(op, c.waves, w, in, bases, out, n, s, nullptr, nullptr, 0, nullptr, c.two_blocks);
+        if (rc >= 0) return rc;
+    }
+    return run_stream<T>(cell, in, out, bases, 0, n, need_in, need_out, op != OP_TRANSPOSE && op != OP_UNTRANSPOSE, s);
+}
+
 // Uniform-width call served by the wave-per-block kernels (fl_dispatch.hpp decides; 0 waves = cell-column kernel).
 template <typename T>
 int run_wave_uniform(bool pack, int waves, unsigned w, const T* packed, T* unpacked, const T* refs, size_t ref_stride,
@@ -145,99 +205,86 @@ int run_wave_uniform(bool pack, int waves, unsigned w, const T* packed, T* unpac
     if (n_blocks == 0 || (pack && w == 0)) return FL_OK;
     if (!unpacked || (w != 0 && !packed)) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(unpacked)) return FL_ERR_ALIGN;
-    WidthsArgs a;
-    a.packed = reinterpret_cast<const char*>(packed);
-    a.unpacked = reinterpret_cast<char*>(unpacked);
-    a.widths = nullptr;
-    a.offsets = nullptr;
-    a.err_flag = nullptr;
-    a.refs = refs;
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = w;
     const unsigned bpw = uniform_blocks_per_wave(Elem<T>::BITS, pack, w, refs != nullptr);
     const WaveShape sh = with_policy({waves, bpw, bpw > 1});
-    a.bpw = sh.bpw;
-    a.packed_bytes = 0;      // not read: uniform-width calls are validated here, on the host side
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = fl::nt_read_from(Elem<T>::BITS);
+    WidthsArgs a;
+    widths_args<T>(a, {false, w}, packed, unpacked, refs, ref_stride, nullptr, n_blocks, sh);
     return hip_status(widths_launcher<T>(pack)(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// THE path of the seven uniform-width entry points: the width check, the policy's choice (chosen_waves), the wave-per-block kernel, and
+// otherwise run_stream on the family's cell-column instance cell.fn[w].  `aux` is FoR's references or Delta's bases.  chain_op < 0:
+// BitPacking / FoR on widths_launcher; else Delta's op on the pipeline kernel, which alone may take the table's two-blocks form.
+// The order of the checks is each path's own, and the status of a call with two faults depends on it.
+template <typename T>
+int run_uniform(WaveOp op, int chain_op, const WidthTable<T>& cell, unsigned w, const T* in, const T* aux, size_t aux_stride, T* out,
+                size_t n, void* s, bool two_blocks = false)
+{
+    if (over_width<T>(w)) return FL_ERR_WIDTH;
+    const bool pack = op == WAVE_PACK || op == WAVE_FOR_PACK || op == WAVE_TRANSPOSE_DELTA_PACK;
+    const bool need_aux = op != WAVE_PACK && op != WAVE_UNPACK;
+    const bool need_in = pack || w != 0, need_out = !pack || w != 0;          // the packed side of a W = 0 column has no bytes
+    WaveChoice c = chosen_waves(Elem<T>::BITS, w, op);
+    if (chain_op >= 0) {
+        if (n && misaligned(aux)) return FL_ERR_ALIGN;                         // Delta: the bases' alignment before anything but the width
+        c.two_blocks = c.two_blocks && two_blocks;
+        return run_chain_or_stream<T>(chain_op, c, w, cell.fn[w], in, aux, out, n, need_in, need_out, s);
+    }
+    if (c.waves) {
+        // before run_wave_uniform's early FL_OK for a W = 0 pack: the unpacked input of a pack and FoR's references are always needed
+        if (n && ((pack && !in) || (need_aux && !aux))) return FL_ERR_NULL;
+        return pack ? run_wave_uniform<T>(true, c.waves, w, out, const_cast<T*>(in), aux, aux_stride, n, s)
+                    : run_wave_uniform<T>(false, c.waves, w, in, out, aux, aux_stride, n, s);
+    }
+    return run_stream<T>(cell.fn[w], in, out, aux, aux_stride, n, need_in, need_out, need_aux, s);
 }
 
 template <typename T> int dev_pack(unsigned w, const T* in, T* out, size_t n, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_PACK).waves) {
-        if (n && !in) return FL_ERR_NULL;
-        return run_wave_uniform<T>(true, waves, w, out, const_cast<T*>(in), nullptr, 0, n, s);
-    }
-    return run_stream<T>(pack_table_impl<T, PACK_PLAIN>().fn[w], in, out, nullptr, 0, n, true, w != 0, false, s);
+    return run_uniform<T>(WAVE_PACK, -1, pack_table_impl<T, PACK_PLAIN>(), w, in, nullptr, 0, out, n, s);
 }
 template <typename T> int dev_unpack(unsigned w, const T* in, T* out, size_t n, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNPACK).waves)
-        return run_wave_uniform<T>(false, waves, w, in, out, nullptr, 0, n, s);
-    return run_stream<T>(unpack_table_impl<T, BODY_STORE>().fn[w], in, out, nullptr, 0, n, w != 0, true, false, s);
+    return run_uniform<T>(WAVE_UNPACK, -1, unpack_table_impl<T, BODY_STORE>(), w, in, nullptr, 0, out, n, s);
 }
-template <typename T>
-int dev_for_pack(unsigned w, const T* in, const T* refs, size_t stride, T* out, size_t n, void* s)
+template <typename T> int dev_for_pack(unsigned w, const T* in, const T* refs, size_t stride, T* out, size_t n, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_FOR_PACK).waves) {
-        if (n && (!in || !refs)) return FL_ERR_NULL;
-        return run_wave_uniform<T>(true, waves, w, out, const_cast<T*>(in), refs, stride, n, s);
-    }
-    return run_stream<T>(pack_table_impl<T, PACK_FOR>().fn[w], in, out, refs, stride, n, true, w != 0, true, s);
+    return run_uniform<T>(WAVE_FOR_PACK, -1, pack_table_impl<T, PACK_FOR>(), w, in, refs, stride, out, n, s);
 }
-template <typename T>
-int dev_unfor_pack(unsigned w, const T* in, const T* refs, size_t stride, T* out, size_t n, void* s)
+template <typename T> int dev_unfor_pack(unsigned w, const T* in, const T* refs, size_t stride, T* out, size_t n, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNFOR_PACK).waves) {
-        if (n && !refs) return FL_ERR_NULL;
-        return run_wave_uniform<T>(false, waves, w, in, out, refs, stride, n, s);
-    }
-    return run_stream<T>(unpack_table_impl<T, BODY_ADD_REF>().fn[w], in, out, refs, stride, n, w != 0, true, true, s);
+    return run_uniform<T>(WAVE_UNFOR_PACK, -1, unpack_table_impl<T, BODY_ADD_REF>(), w, in, refs, stride, out, n, s);
 }
-template <typename T>
-int dev_undelta_pack(unsigned w, const T* in, const T* bases, T* out, size_t n, void* s)
+template <typename T> int dev_undelta_pack(unsigned w, const T* in, const T* bases, T* out, size_t n, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    return run_uniform<T>(WAVE_UNDELTA_PACK, OP_UNDELTA_PACK, unpack_table_impl<T, BODY_UNDELTA>(), w, in, bases, 0, out, n, s, true);
+}
+template <typename T> int dev_undelta_pack_untranspose(unsigned w, const T* in, const T* bases, T* out, size_t n, void* s)
+{
+    return run_uniform<T>(WAVE_UNDELTA_PACK_UNTRANSPOSE, OP_UNDELTA_PACK_UNTRANSPOSE, unpack_table_impl<T, BODY_UNDELTA_UNTRANSPOSE>(), w, in, bases,
+                          0, out, n, s);
+}
+template <typename T> int dev_transpose_delta_pack(unsigned w, const T* in, const T* bases, T* out, size_t n, void* s)
+{
+    return run_uniform<T>(WAVE_TRANSPOSE_DELTA_PACK, OP_TRANSPOSE_DELTA_PACK, pack_table_impl<T, PACK_TRANSPOSE_DELTA>(), w, in, bases, 0, out, n, s);
+}
+// Delta's and Transpose's own bodies have no width: their table row is read at W = T, and the cell-column kernel is per type
+template <typename T> int dev_delta(bool inverse, const T* in, const T* bases, T* out, size_t n, void* s)
+{
     if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const WaveChoice c = chosen_waves(Elem<T>::BITS, w, WAVE_UNDELTA_PACK); c.waves) {
-        const int rc = run_chain<T>(OP_UNDELTA_PACK, c.waves, w, in, bases, out, n, s, nullptr, nullptr, 0, nullptr, c.two_blocks);
-        if (rc >= 0) return rc;                  // -1: no pipeline form of this op (cannot happen today): the cell-column kernel
-    }
-    return run_stream<T>(unpack_table_impl<T, BODY_UNDELTA>().fn[w], in, out, bases, 0, n, w != 0, true, true, s);
+    const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNDELTA : WAVE_DELTA).waves;
+    return run_chain_or_stream<T>(inverse ? OP_UNDELTA : OP_DELTA, {waves, false}, Elem<T>::BITS, delta_launcher<T>(inverse), in, bases, out, n, true, true, s);
 }
-template <typename T>
-int dev_undelta_pack_untranspose(unsigned w, const T* in, const T* bases, T* out, size_t n, void* s)
+template <typename T> int dev_transpose(bool inverse, const T* in, T* out, size_t n, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_UNDELTA_PACK_UNTRANSPOSE).waves) {
-        const int rc = run_chain<T>(OP_UNDELTA_PACK_UNTRANSPOSE, waves, w, in, bases, out, n, s);
-        if (rc >= 0) return rc;
-    }
-    return run_stream<T>(unpack_table_impl<T, BODY_UNDELTA_UNTRANSPOSE>().fn[w], in, out, bases, 0, n, w != 0, true, true, s);
-}
-template <typename T>
-int dev_transpose_delta_pack(unsigned w, const T* in, const T* bases, T* out, size_t n, void* s)
-{
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const int waves = chosen_waves(Elem<T>::BITS, w, WAVE_TRANSPOSE_DELTA_PACK).waves) {
-        const int rc = run_chain<T>(OP_TRANSPOSE_DELTA_PACK, waves, w, in, bases, out, n, s);
-        if (rc >= 0) return rc;
-    }
-    return run_stream<T>(pack_table_impl<T, PACK_TRANSPOSE_DELTA>().fn[w], in, out, bases, 0, n, true, w != 0, true, s);
+    const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNTRANSPOSE : WAVE_TRANSPOSE).waves;
+    return run_chain_or_stream<T>(inverse ? OP_UNTRANSPOSE : OP_TRANSPOSE, {waves, false}, Elem<T>::BITS, transpose_launcher<T>(inverse), in,
+                                  static_cast<const T*>(nullptr), out, n, true, true, s);
 }
 template <typename T>
 int dev_unpack_block_sums(unsigned w, const T* in, size_t n, uint64_t* sums, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (over_width<T>(w)) return FL_ERR_WIDTH;
     if (n == 0) return FL_OK;
     if (!sums || (w != 0 && !in)) return FL_ERR_NULL;
     if (misaligned(in)) return FL_ERR_ALIGN;
@@ -247,7 +294,7 @@ int dev_unpack_block_sums(unsigned w, const T* in, size_t n, uint64_t* sums, voi
 template <typename T>
 int dev_unpack_compare(unsigned w, const T* in, int op, T constant, size_t n, uint32_t* mask, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (over_width<T>(w)) return FL_ERR_WIDTH;
     if (op < FL_CMP_EQ || op > FL_CMP_GE) return FL_ERR_INDEX;
     if (n == 0) return FL_OK;
     if (!mask || (w != 0 && !in)) return FL_ERR_NULL;
@@ -285,28 +332,11 @@ int dev_block_min_max(const T* in, size_t n, T* mins, T* maxs, void* s)
     ReduceArgs a{reinterpret_cast<const u32x4*>(in), mins, maxs, n};
     return hip_status(min_max_launcher<T>()(a, static_cast<hipStream_t>(s)));
 }
-template <typename T> int dev_delta(bool inverse, const T* in, const T* bases, T* out, size_t n, void* s)
-{
-    if (n && misaligned(bases)) return FL_ERR_ALIGN;
-    if (const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNDELTA : WAVE_DELTA).waves) {
-        const int rc = run_chain<T>(inverse ? OP_UNDELTA : OP_DELTA, waves, Elem<T>::BITS, in, bases, out, n, s);
-        if (rc >= 0) return rc;
-    }
-    return run_stream<T>(delta_launcher<T>(inverse), in, out, bases, 0, n, true, true, true, s);
-}
-template <typename T> int dev_transpose(bool inverse, const T* in, T* out, size_t n, void* s)
-{
-    if (const int waves = chosen_waves(Elem<T>::BITS, Elem<T>::BITS, inverse ? WAVE_UNTRANSPOSE : WAVE_TRANSPOSE).waves) {
-        const int rc = run_chain<T>(inverse ? OP_UNTRANSPOSE : OP_TRANSPOSE, waves, Elem<T>::BITS, in, static_cast<const T*>(nullptr), out, n, s);
-        if (rc >= 0) return rc;
-    }
-    return run_stream<T>(transpose_launcher<T>(inverse), in, out, nullptr, 0, n, true, true, false, s);
-}
 template <typename T>
 int dev_unpack_single(unsigned w, const T* packed, size_t n_blocks, const uint64_t* idx, size_t n_idx,
                       T* out, uint32_t* err_flag, void* s)
 {
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (over_width<T>(w)) return FL_ERR_WIDTH;
     if (n_idx == 0) return FL_OK;
     if (!idx || !out || (w != 0 && !packed)) return FL_ERR_NULL;
     SingleArgs a{packed, idx, out, err_flag, n_blocks, n_idx, w, nullptr, nullptr, 0};
@@ -318,253 +348,25 @@ int dev_unpack_single_widths(const uint8_t* widths, const uint64_t* offsets, con
                              const uint64_t* idx, size_t n_idx, T* out, uint32_t* err_flag, void* s)
 {
     if (n_idx == 0) return FL_OK;
-    static const T no_bytes[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-    if (!packed && packed_bytes == 0) packed = no_bytes;      // a column of width-0 blocks has no packed bytes (every lookup is 0)
+    if (!packed && packed_bytes == 0) packed = no_bytes<T>();      // a column of width-0 blocks has no packed bytes (every lookup is 0)
     if (!widths || !offsets || !idx || !out || !packed) return FL_ERR_NULL;
     SingleArgs a{packed, idx, out, err_flag, n_blocks, n_idx, 0, widths, offsets, packed_bytes};
     return hip_status(unpack_single_launch<T>(a, static_cast<hipStream_t>(s)));
 }
 
-// ---------------------------------------------------------------------------
-// Host tier: the trait methods' host slices, run through the same kernels.
-//
-// The reference is allocation-free (`#![no_std]`, lib.rs:3); so is this tier after its first call
-// on a thread: every host thread keeps ONE cached context (HostCtx, thread_local) holding
-//   * a private non-blocking stream (concurrent host threads do not serialise on the null stream),
-//   * a pinned, device-mapped staging buffer and a device scratch buffer, both grown geometrically
-//     and freed at thread exit or by fl_host_release().
-// Small calls (one trait-method call = one block) are ZERO-COPY: the slices are copied into the
-// pinned buffer and the kernel reads / writes that host memory directly over PCIe -- one launch, no DMA
-// round trips, completion signalled through a word in pinned memory (HostCtx::wait_zero_copy).  Large calls
-// stage through the device scratch buffer.
-// ---------------------------------------------------------------------------
-// the last thing queued behind a zero-copy call: one thread stores the call's sequence number into pinned host memory
-__global__ void k_host_done(uint64_t* flag, uint64_t seq)
-{
-    __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// zero-copy calls whose completion word did not arrive within the spin's bound (each cost a 50 ms stall and a real synchronise):
-// fl_internal_zero_copy_fallbacks() -- a 50-ms-per-call cliff must not be silent
-std::atomic<uint64_t> g_zero_copy_fallbacks{0};
-
-struct HostCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    char* dev = nullptr;
-    size_t dev_cap = 0;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    uint64_t* done = nullptr;      // pinned: the sequence number of the last finished zero-copy call (k_host_done)
-    uint64_t seq = 0;
-    unsigned since_sync = 0;
-
-    // Best effort: runs from fl_host_release() and from the thread_local destructor, i.e. possibly while the process is
-    // tearing down.  If the runtime no longer answers (hipGetDevice fails) or the context's device cannot be made current,
-    // nothing is freed -- leaking at exit is harmless, calling into a torn-down runtime is not.  Long-lived worker
-    // threads should call fl_host_release() themselves before they exit.
-    void release()
-    {
-        if (device < 0) return;
-        int cur = -1;
-        bool usable = hipGetDevice(&cur) == hipSuccess;
-        bool switched = false;
-        if (usable && cur != device) usable = switched = hipSetDevice(device) == hipSuccess;
-        if (usable) {
-            if (stream) (void)hipStreamSynchronize(stream);
-            if (stream) (void)hipStreamDestroy(stream);
-            if (dev) (void)hipFree(dev);
-            if (pin) (void)hipHostFree(pin);
-            if (done) (void)hipHostFree(done);
-            if (switched) (void)hipSetDevice(cur);
-        }
-        stream = nullptr; dev = nullptr; pin = nullptr; done = nullptr;
-        dev_cap = pin_cap = 0;
-        seq = 0; since_sync = 0;
-        device = -1;
-    }
-    // Completion of everything queued on `stream` by a ZERO-COPY call (its results are in pinned host memory once the kernel has
-    // retired).  hipStreamSynchronize costs ~9 of such a call's 13 us; a one-thread kernel queued behind the work that stores the
-    // call's sequence number into pinned memory, and a host spin on that word, cost ~2.4 us less (tools/exp_host_sync.hip,
-    // profiles/exp_host_sync_r04.txt: 13.1 -> 10.7 us).  The spin is bounded: if the number has not arrived after ~50 ms -- a kernel
-    // that faulted never stores it -- or the marker cannot be launched, the stream is synchronised the ordinary way, which also
-    // reports the error.  Every 4096th call synchronises for real so that the runtime retires its completion records.
-    hipError_t wait_zero_copy()
-    {
-        if (!done || ++since_sync >= 4096) { since_sync = 0; return hipStreamSynchronize(stream); }
-        const uint64_t want = ++seq;
-        FL_LAUNCH(k_host_done, dim3(1), dim3(1), 0, stream, done, want);
-        if (hipGetLastError() != hipSuccess) return hipStreamSynchronize(stream);
-        std::chrono::steady_clock::time_point t0;
-        for (unsigned spins = 0;; ++spins) {
-            if (__atomic_load_n(done, __ATOMIC_ACQUIRE) == want) return hipSuccess;
-            if ((spins & 0xffffu) == 0xffffu) {                   // every 65 536 polls (some tens of us): look at the clock
-                const auto now = std::chrono::steady_clock::now();
-                if (spins == 0xffffu) t0 = now;
-                else if (now - t0 > std::chrono::milliseconds(50)) {                  // never seen in a healthy run: make it visible
-                    g_zero_copy_fallbacks.fetch_add(1, std::memory_order_relaxed);
-                    return hipStreamSynchronize(stream);
-                }
-            }
-        }
-    }
-    // bind to the calling thread's current device
-    hipError_t bind()
-    {
-        int cur = 0;
-        hipError_t e = hipGetDevice(&cur);
-        if (e != hipSuccess) return e;
-        if (cur == device) return hipSuccess;
-        release();
-        e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { stream = nullptr; return e; }
-        device = cur;
-        // fine-grained (coherent) and mapped, explicitly: the host must SEE the marker's system-scope store without a synchronising
-        // call, which hipHostMallocDefault only implies
-        if (hipHostMalloc(reinterpret_cast<void**>(&done), 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) *done = 0;
-        else { done = nullptr; (void)hipGetLastError(); }          // no marker word: wait_zero_copy() synchronises the stream instead
-        seq = 0;
-        return hipSuccess;
-    }
-    static size_t grown(size_t need, size_t have) { return need > 2 * have ? need : 2 * have; }
-    hipError_t need_pinned(size_t bytes)
-    {
-        if (bytes <= pin_cap) return hipSuccess;
-        if (pin) {
-            hipError_t es = hipStreamSynchronize(stream);          // a kernel may still be using the old buffer
-            if (es != hipSuccess) return es;
-            (void)hipHostFree(pin); pin = nullptr; pin_cap = 0;
-        }
-        const size_t cap = grown(bytes, pin_cap < 65536 ? 65536 : pin_cap);
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&pin), cap, hipHostMallocCoherent | hipHostMallocMapped);   // see `done`
-        if (e == hipSuccess) pin_cap = cap; else pin = nullptr;
-        return e;
-    }
-    hipError_t need_device(size_t bytes)
-    {
-        if (bytes <= dev_cap) return hipSuccess;
-        if (dev) {
-            hipError_t es = hipStreamSynchronize(stream);
-            if (es != hipSuccess) return es;
-            (void)hipFree(dev); dev = nullptr; dev_cap = 0;
-        }
-        const size_t cap = grown(bytes, dev_cap);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), cap);
-        if (e == hipSuccess) dev_cap = cap; else dev = nullptr;
-        return e;
-    }
-    ~HostCtx() { release(); }
-};
-thread_local HostCtx g_host;
-
-constexpr size_t HOST_ZERO_COPY_LIMIT = 256 * 1024;   // bytes (in + aux + out) served straight from pinned host memory
-
-#define FL_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_); } while (0)
-
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// dev(in, aux, out, stream) launches the device-tier op on pointers the GPU can reach.
-template <typename T, typename F>
-int host_run(const T* in, size_t in_elems, const T* aux, size_t aux_elems, T* out, size_t out_elems, F&& dev)
-{
-    if ((in_elems && !in) || (out_elems && !out) || (aux_elems && !aux)) return FL_ERR_NULL;
-    const size_t ib = in_elems * sizeof(T), ab = aux_elems * sizeof(T), ob = out_elems * sizeof(T);
-    const size_t o_aux = pad256(ib), o_out = o_aux + pad256(ab), total = o_out + pad256(ob);
-    HostCtx& c = g_host;
-    FL_HIP(c.bind());
-    fl::constructed_pair_this_thread() = false;             // the host tier's own staging buffers (a device-tier call may have left it set)
-    if (total <= HOST_ZERO_COPY_LIMIT) {
-        FL_HIP(c.need_pinned(total));
-        if (ib) memcpy(c.pin, in, ib);
-        if (ab) memcpy(c.pin + o_aux, aux, ab);
-        int rc = dev(reinterpret_cast<const T*>(c.pin), reinterpret_cast<const T*>(c.pin + o_aux),
-                     reinterpret_cast<T*>(c.pin + o_out), c.stream);
-        if (rc != FL_OK) return rc;
-        FL_HIP(c.wait_zero_copy());
-        if (ob) memcpy(out, c.pin + o_out, ob);
-        return FL_OK;
-    }
-    FL_HIP(c.need_device(total));
-    if (ib) FL_HIP(hipMemcpyAsync(c.dev, in, ib, hipMemcpyHostToDevice, c.stream));
-    if (ab) FL_HIP(hipMemcpyAsync(c.dev + o_aux, aux, ab, hipMemcpyHostToDevice, c.stream));
-    int rc = dev(reinterpret_cast<const T*>(c.dev), reinterpret_cast<const T*>(c.dev + o_aux),
-                 reinterpret_cast<T*>(c.dev + o_out), c.stream);
-    if (rc != FL_OK) return rc;
-    if (ob) FL_HIP(hipMemcpyAsync(out, c.dev + o_out, ob, hipMemcpyDeviceToHost, c.stream));
-    FL_HIP(hipStreamSynchronize(c.stream));
-    return FL_OK;
-}
-
-// unpack_single on host slices: only the indexed block travels (128*W bytes into the pinned buffer;
-// the kernel then touches the one or two words bitpacking.rs:164-178 reads).
-template <typename T>
-int host_unpack_single(unsigned w, const T* pk, size_t n_blocks, uint64_t index, T* value)
-{
-    if (w > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
-    if (!value) return FL_ERR_NULL;
-    if (w == 0) { *value = 0; return FL_OK; }                 // bitpacking.rs:136-139 precedes the assert
-    if (index >= (uint64_t)n_blocks * 1024) return FL_ERR_INDEX;   // bitpacking.rs:152
-    if (!pk) return FL_ERR_NULL;
-    const size_t pl = (size_t)1024 * w / Elem<T>::BITS, pb = pl * sizeof(T);
-    const size_t o_idx = pad256(pb), o_val = o_idx + 256;
-    HostCtx& c = g_host;
-    FL_HIP(c.bind());
-    FL_HIP(c.need_pinned(o_val + 256));
-    memcpy(c.pin, pk + (index >> 10) * pl, pb);
-    *reinterpret_cast<uint64_t*>(c.pin + o_idx) = index & 1023u;
-    int rc = dev_unpack_single<T>(w, reinterpret_cast<const T*>(c.pin), 1, reinterpret_cast<const uint64_t*>(c.pin + o_idx), 1,
-                                  reinterpret_cast<T*>(c.pin + o_val), nullptr, c.stream);
-    if (rc != FL_OK) return rc;
-    FL_HIP(c.wait_zero_copy());
-    *value = *reinterpret_cast<const T*>(c.pin + o_val);
-    return FL_OK;
-}
-
-template <typename T> size_t plen(unsigned w) { return (size_t)1024 * w / Elem<T>::BITS; }
-
-}  // namespace
-
-// ---------------------------------------------------------------------------
 // mixed-width columns: device-resident widths[] / offsets[] (fl_widths.hpp)
-// ---------------------------------------------------------------------------
-struct fl_mixed_plan {
-    unsigned type_bits = 0;
-    size_t n_blocks = 0;
-    uint64_t packed_bytes = 0;
-    uint8_t* d_widths = nullptr;     // widths[n_blocks] in HBM
-    uint64_t* d_offsets = nullptr;   // byte offset of every block in the packed column (exclusive prefix sum of 128*W)
-};
-
-namespace {
-
 template <typename T>
 int run_widths(bool pack, const uint8_t* widths, const uint64_t* offsets, const void* packed, size_t packed_bytes, void* unpacked,
                size_t n_blocks, uint32_t* err_flag, void* stream, const T* refs = nullptr, size_t ref_stride = 0, bool with_refs = false)
 {
     if (n_blocks == 0) return FL_OK;
     if (with_refs && !refs) return FL_ERR_NULL;
-    // a column whose blocks all have width 0 has no packed bytes at all: its packed pointer may be NULL (any block with a
-    // width > 0 then fails the kernel's bounds check against packed_bytes == 0)
-    static const char no_bytes[16] __attribute__((aligned(16))) = {0};
-    if (!packed && packed_bytes == 0) packed = no_bytes;
+    if (!packed && packed_bytes == 0) packed = no_bytes<T>();    // a column whose blocks all have width 0: its packed pointer may be NULL
     if (!widths || !offsets || !packed || !unpacked) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(unpacked)) return FL_ERR_ALIGN;
-    WidthsArgs a;
-    a.packed = static_cast<const char*>(packed);
-    a.unpacked = static_cast<char*>(unpacked);
-    a.widths = widths;
-    a.offsets = offsets;
-    a.err_flag = err_flag;
-    a.refs = with_refs ? refs : nullptr;
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = 0;
-    a.packed_bytes = packed_bytes;
     const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, pack), mixed_blocks_per_wave(Elem<T>::BITS, pack), mixed_prefetch(Elem<T>::BITS)});
-    a.bpw = sh.bpw;
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = 0;           // a mixed-width column always streams
+    WidthsArgs a;
+    widths_args<T>(a, {true, 0, widths, offsets, packed_bytes}, packed, unpacked, with_refs ? refs : nullptr, ref_stride, err_flag, n_blocks, sh);
     return hip_status(widths_launcher<T>(pack)(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
@@ -582,59 +384,36 @@ int run_chain_widths(int op, const uint8_t* widths, const uint64_t* offsets, con
 }
 
 // The four consumers of a FoR-packed column (fl_for_block.hpp): unfor_compare, unfor_compare_range, unfor_select, unfor_aggregate, each over
-// a uniform-width column (mixed = false: `width`, blocks back to back) or a mixed-width one (widths[] / offsets[], checked per block by the
-// kernel).  16 aligned zero bytes stand in for a buffer that has none.
-template <typename T> const T* no_bytes()
-{
-    static const T zeros[16 / sizeof(T)] __attribute__((aligned(16))) = {0};
-    return zeros;
-}
+// a uniform-width column (col.width, blocks back to back) or a mixed-width one (widths[] / offsets[], checked per block by the kernel).
 // false: one of the column's pointers is missing (FL_ERR_NULL).  A mixed-width column whose blocks all have width 0 has no packed bytes:
 // its packed pointer may be NULL (run_widths) and is replaced here.
-template <typename T>
-bool block_consumer_column(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T*& packed, size_t packed_bytes, const T* refs)
+template <typename T> bool block_consumer_column(const Column& col, const T*& packed, const T* refs)
 {
-    if (mixed && !packed && packed_bytes == 0) packed = no_bytes<T>();
-    return refs && (!mixed || (widths && offsets)) && (packed || (!mixed && width == 0));
+    if (col.mixed && !packed && col.packed_bytes == 0) packed = no_bytes<T>();
+    return refs && (!col.mixed || (col.widths && col.offsets)) && (packed || (!col.mixed && col.width == 0));
 }
 // the WidthsArgs part of the four argument blocks, launched with the shape of unfor_pack_widths: the same blocks, the same reads
 template <typename T>
-WaveShape block_consumer_args(WidthsArgs& a, bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed,
-                              size_t packed_bytes, size_t ref_stride, size_t n_blocks, uint32_t* err_flag)
+WaveShape block_consumer_args(WidthsArgs& a, const Column& col, const T* packed, size_t ref_stride, size_t n_blocks, uint32_t* err_flag)
 {
-    a.packed = reinterpret_cast<const char*>(packed);
-    a.unpacked = nullptr;
-    a.widths = mixed ? widths : nullptr;
-    a.offsets = mixed ? offsets : nullptr;
-    a.err_flag = err_flag;
-    a.refs = nullptr;                        // the kernel loads the references with the block's metadata
-    a.ref_stride = ref_stride;
-    a.n_blocks = n_blocks;
-    a.uniform_width = mixed ? 0u : width;
-    a.packed_bytes = mixed ? packed_bytes : 0;   // a uniform-width call is validated on the host side
     const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
-    a.bpw = sh.bpw;
-    a.prefetch = sh.prefetch;
-    a.linear_map = 0;
-    a.nt_from = mixed ? 0u : fl::nt_read_from(Elem<T>::BITS);   // a mixed-width column always streams
+    widths_args<T>(a, col, packed, nullptr, nullptr, ref_stride, err_flag, n_blocks, sh);
     return sh;
 }
 
-// unfor_compare over a uniform-width column (mixed = false: `width`, blocks back to back) or a mixed-width one (widths[] / offsets[],
-// checked per block by the kernel); fl_for_compare.hpp.  The predicate becomes its cyclic interval here, once per call.
+// unfor_compare (fl_for_compare.hpp).  The predicate becomes its cyclic interval here, once per call.
 template <typename T>
-int run_unfor_compare(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
-                      const T* refs, size_t ref_stride, int op, T constant, size_t n_blocks, uint32_t* mask, uint32_t* err_flag,
-                      void* stream)
+int run_unfor_compare(const Column& col, const T* packed, const T* refs, size_t ref_stride, int op, T constant, size_t n_blocks,
+                      uint32_t* mask, uint32_t* err_flag, void* stream)
 {
-    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
     if (op < FL_CMP_EQ || op > FL_CMP_GE) return FL_ERR_INDEX;
     if (n_blocks == 0) return FL_OK;
-    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !mask) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs) || !mask) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask)) return FL_ERR_ALIGN;
     const ForPredicate p = for_compare_predicate(Elem<T>::BITS, op, constant);
     ForCompareArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, mixed ? err_flag : nullptr);
+    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
     a.mask = reinterpret_cast<char*>(mask);
     a.cmp_refs = refs;
     a.cmp_a = p.a;
@@ -643,24 +422,22 @@ int run_unfor_compare(bool mixed, unsigned width, const uint8_t* widths, const u
     return hip_status(for_compare_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
-// unfor_compare_range over a uniform-width column (mixed = false) or a mixed-width one: run_unfor_compare with the cyclic interval
-// [lo, hi] as the predicate and the mask so far beside it (fl_for_compare_range.hpp).  The same launch shape, the same checks in the
-// same order; `mask` may be `mask_in`.
+// unfor_compare_range: run_unfor_compare with the cyclic interval [lo, hi] as the predicate and the mask so far beside it
+// (fl_for_compare_range.hpp).  The same launch shape, the same checks in the same order; `mask` may be `mask_in`.
 template <typename T>
-int run_unfor_compare_range(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
-                            const T* refs, size_t ref_stride, T lo, T hi, int combine, const uint32_t* mask_in, size_t n_blocks,
-                            uint32_t* mask, uint32_t* err_flag, void* stream)
+int run_unfor_compare_range(const Column& col, const T* packed, const T* refs, size_t ref_stride, T lo, T hi, int combine,
+                            const uint32_t* mask_in, size_t n_blocks, uint32_t* mask, uint32_t* err_flag, void* stream)
 {
-    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
     if (combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
     if (n_blocks == 0) return FL_OK;
     if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
     else if (!mask_in) return FL_ERR_NULL;
-    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !mask) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs) || !mask) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
     const ForPredicate p = for_range_predicate(Elem<T>::BITS, lo, hi);
     ForRangeArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, mixed ? err_flag : nullptr);
+    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
     a.mask = reinterpret_cast<char*>(mask);
     a.cmp_refs = refs;
     a.cmp_a = p.a;
@@ -671,22 +448,21 @@ int run_unfor_compare_range(bool mixed, unsigned width, const uint8_t* widths, c
     return hip_status(for_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
-// unfor_select over a uniform-width column (mixed = false) or a mixed-width one (widths[] / offsets[], checked per block by the kernel);
-// fl_select.hpp.  Launched with the shape of unfor_pack_widths, as unfor_compare is.
+// unfor_select (fl_select.hpp).  Launched with the shape of unfor_pack_widths, as unfor_compare is.
 template <typename T>
-int run_unfor_select(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
-                     const T* refs, size_t ref_stride, const uint32_t* mask, const uint64_t* out_offsets, T* out, size_t out_len,
-                     size_t n_blocks, uint32_t* err_flag, void* stream)
+int run_unfor_select(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, const uint64_t* out_offsets,
+                     T* out, size_t out_len, size_t n_blocks, uint32_t* err_flag, void* stream)
 {
-    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
     if (n_blocks == 0) return FL_OK;
     // a selection that keeps nothing has no output: `out` may be NULL with out_len == 0 (a non-empty block then fails the kernel's
     // bounds check; nothing is ever written through this pointer)
     if (!out && out_len == 0) out = const_cast<T*>(no_bytes<T>());
-    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !mask || !out_offsets || !out) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs) || !mask || !out_offsets || !out) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask) || misaligned(out)) return FL_ERR_ALIGN;
     SelectArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, err_flag);   // the uniform form raises FL_DEVERR_BOUNDS too (a run outside `out`)
+    // err_flag for a uniform-width column too, the only consumer that takes one: this form raises FL_DEVERR_BOUNDS (a run outside `out`)
+    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, err_flag);
     a.mask = mask;
     a.out_offsets = out_offsets;
     a.out = reinterpret_cast<char*>(out);
@@ -695,20 +471,18 @@ int run_unfor_select(bool mixed, unsigned width, const uint8_t* widths, const ui
     return hip_status(select_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
-// unfor_aggregate over a uniform-width column (mixed = false) or a mixed-width one (widths[] / offsets[], checked per block by the kernel:
-// a failing block's slot receives the identity); fl_aggregate.hpp.  Launched with the shape of unfor_pack_widths, as unfor_select is.
-// `mask` may be NULL: every row is kept and no mask is read.
+// unfor_aggregate (fl_aggregate.hpp: a block that fails the kernel's checks leaves the identity in its slot).  Launched with the shape of
+// unfor_pack_widths, as unfor_select is.  `mask` may be NULL: every row is kept and no mask is read.
 template <typename T>
-int run_unfor_aggregate(bool mixed, unsigned width, const uint8_t* widths, const uint64_t* offsets, const T* packed, size_t packed_bytes,
-                        const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, void* block_aggs, uint32_t* err_flag,
-                        void* stream)
+int run_unfor_aggregate(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks,
+                        void* block_aggs, uint32_t* err_flag, void* stream)
 {
-    if (!mixed && width > (unsigned)Elem<T>::BITS) return FL_ERR_WIDTH;
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
     if (n_blocks == 0) return FL_OK;
-    if (!block_consumer_column(mixed, width, widths, offsets, packed, packed_bytes, refs) || !block_aggs) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs) || !block_aggs) return FL_ERR_NULL;
     if (misaligned(packed) || misaligned(mask) || misaligned(block_aggs)) return FL_ERR_ALIGN;
     AggregateArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, mixed, width, widths, offsets, packed, packed_bytes, ref_stride, n_blocks, mixed ? err_flag : nullptr);
+    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
     a.mask = mask;
     a.aggs = static_cast<char*>(block_aggs);
     a.agg_refs = refs;
@@ -722,7 +496,25 @@ template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n,
     return hip_status(launch_for_widths<T>(mins, maxs, n, widths, static_cast<hipStream_t>(s)));
 }
 
-// many small arrays, device arrays of pointers (fl_batch.hpp)
+// THE place that fills a BatchArgs: many small arrays, device arrays of pointers (fl_batch.hpp).  refs: FoR's; bases: Delta's.
+inline void batch_args(BatchArgs& b, const void* const* packed, void* const* unpacked, const uint8_t* widths, const void* refs,
+                       const void* const* bases, const uint32_t* n_blocks, size_t n_arrays, uint32_t max_blocks, uint32_t* err_flag,
+                       const WaveShape& sh)
+{
+    b.packed = reinterpret_cast<const char* const*>(packed);
+    b.unpacked = reinterpret_cast<char* const*>(unpacked);
+    b.widths = widths;
+    b.n_blocks = n_blocks;
+    b.err_flag = err_flag;
+    b.refs = refs;
+    b.bases = reinterpret_cast<const char* const*>(bases);
+    b.n_arrays = n_arrays;
+    b.tiles_per_array = 0;
+    b.max_blocks = max_blocks;
+    b.bpw = sh.bpw;
+    b.prefetch = sh.prefetch;
+}
+
 template <typename T>
 int run_batch(bool pack, const void* const* packed, void* const* unpacked, const uint8_t* widths, const void* refs, bool with_refs,
               const uint32_t* n_blocks, size_t n_arrays, uint32_t max_blocks, uint32_t* err_flag, void* stream)
@@ -730,21 +522,10 @@ int run_batch(bool pack, const void* const* packed, void* const* unpacked, const
     if (n_arrays == 0 || max_blocks == 0) return FL_OK;
     if (!packed || !unpacked || !widths || !n_blocks || (with_refs && !refs)) return FL_ERR_NULL;
     if (max_blocks > BATCH_MAX_BLOCKS) return FL_ERR_INDEX;       // 2^30 blocks = 2^40 values in ONE array: a bound nobody means
-    BatchArgs b;
-    b.packed = reinterpret_cast<const char* const*>(packed);
-    b.unpacked = reinterpret_cast<char* const*>(unpacked);
-    b.widths = widths;
-    b.n_blocks = n_blocks;
-    b.err_flag = err_flag;
-    b.refs = with_refs ? refs : nullptr;
-    b.bases = nullptr;
-    b.n_arrays = n_arrays;
-    b.tiles_per_array = 0;
-    b.max_blocks = max_blocks;
     const unsigned bpw = batch_blocks_per_wave(Elem<T>::BITS, pack);
     const WaveShape sh = with_policy({batch_waves(Elem<T>::BITS, pack), bpw, bpw > 1});
-    b.bpw = sh.bpw;
-    b.prefetch = sh.prefetch;
+    BatchArgs b;
+    batch_args(b, packed, unpacked, widths, with_refs ? refs : nullptr, nullptr, n_blocks, n_arrays, max_blocks, err_flag, sh);
     return hip_status(batch_launcher<T>(pack)(b, max_blocks, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
@@ -758,22 +539,27 @@ int run_batch_chain(int op, const void* const* packed, const void* const* bases,
     if (max_blocks > BATCH_MAX_BLOCKS) return FL_ERR_INDEX;
     const batch_launch_t fn = batch_chain_launcher<T>(op);
     if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
+    // one block per wavefront, no prefetch, whatever the policy says: of its overrides the kernel takes the waves alone
+    const WaveShape sh{with_policy({mixed_waves(Elem<T>::BITS, op == OP_TRANSPOSE_DELTA_PACK)}).waves, 1, 0};
     BatchArgs b;
-    b.packed = reinterpret_cast<const char* const*>(packed);
-    b.unpacked = reinterpret_cast<char* const*>(unpacked);
-    b.widths = widths;
-    b.n_blocks = n_blocks;
-    b.err_flag = err_flag;
-    b.refs = nullptr;
-    b.bases = reinterpret_cast<const char* const*>(bases);
-    b.n_arrays = n_arrays;
-    b.tiles_per_array = 0;
-    b.max_blocks = max_blocks;
-    b.bpw = 1;
-    b.prefetch = 0;
-    const int waves = with_policy({mixed_waves(Elem<T>::BITS, op == OP_TRANSPOSE_DELTA_PACK)}).waves;
-    return hip_status(fn(b, max_blocks, waves, static_cast<hipStream_t>(stream)));
+    batch_args(b, packed, unpacked, widths, nullptr, bases, n_blocks, n_arrays, max_blocks, err_flag, sh);
+    return hip_status(fn(b, max_blocks, sh.waves, static_cast<hipStream_t>(stream)));
 }
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// mixed-width columns with the widths kept by the library: device-resident widths[] / offsets[] behind a handle
+// ---------------------------------------------------------------------------
+struct fl_mixed_plan {
+    unsigned type_bits = 0;
+    size_t n_blocks = 0;
+    uint64_t packed_bytes = 0;
+    uint8_t* d_widths = nullptr;     // widths[n_blocks] in HBM
+    uint64_t* d_offsets = nullptr;   // byte offset of every block in the packed column (exclusive prefix sum of 128*W)
+};
+
+namespace {
 
 template <typename T>
 int run_mixed(bool pack, const fl_mixed_plan* p, const void* packed, void* unpacked, void* stream)
@@ -786,6 +572,19 @@ int run_mixed(bool pack, const fl_mixed_plan* p, const void* packed, void* unpac
     return run_widths<T>(pack, p->d_widths, p->d_offsets, p->packed_bytes ? packed : nullptr, p->packed_bytes, unpacked, p->n_blocks, nullptr, stream);
 }
 
+// the A/B tools' timed call (fl_internal_selftune_check): what the public entry point of (T, op) does
+template <typename T>
+int selftune_call(int op, unsigned w, const void* in, const void* aux, void* out, size_t n, void* s)
+{
+    if (op == 2) {
+        FL_DEVICE_TIER(s, in, aux, out);
+        return dev_undelta_pack<T>(w, static_cast<const T*>(in), static_cast<const T*>(aux), static_cast<T*>(out), n, s);
+    }
+    FL_DEVICE_TIER(s, in, out);
+    return op == 1 ? dev_pack<T>(w, static_cast<const T*>(in), static_cast<T*>(out), n, s)
+                   : dev_unpack<T>(w, static_cast<const T*>(in), static_cast<T*>(out), n, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -793,7 +592,7 @@ extern "C" {
 int fl_widths_to_offsets(unsigned type_bits, const uint8_t* widths, size_t n_blocks, uint64_t* offsets,
                          uint64_t* total_bytes, uint32_t* err_flag, void* stream)
 {
-    if (type_bits != 8 && type_bits != 16 && type_bits != 32 && type_bits != 64) return FL_ERR_WIDTH;
+    if (!valid_type_bits(type_bits)) return FL_ERR_WIDTH;
     if (n_blocks && (!widths || !offsets)) return FL_ERR_NULL;
     FL_DEVICE_TIER(stream, widths, offsets, total_bytes, err_flag);
     ScanArgs a{widths, offsets, total_bytes, err_flag, n_blocks, type_bits};
@@ -817,11 +616,18 @@ int fl_aggregate_reduce(const void* block_aggs, size_t n_blocks, void* result, v
                                               static_cast<hipStream_t>(stream)));
 }
 
+void fl_mixed_plan_destroy(fl_mixed_plan* p)
+{
+    if (!p) return;
+    if (p->d_widths) (void)hipFree(p->d_widths);
+    if (p->d_offsets) (void)hipFree(p->d_offsets);
+    delete p;
+}
 int fl_mixed_plan_create(unsigned type_bits, const uint8_t* widths, size_t n_blocks, fl_mixed_plan** plan)
 {
     if (!plan || (n_blocks && !widths)) return FL_ERR_NULL;
     *plan = nullptr;
-    if (type_bits != 8 && type_bits != 16 && type_bits != 32 && type_bits != 64) return FL_ERR_WIDTH;
+    if (!valid_type_bits(type_bits)) return FL_ERR_WIDTH;
     for (size_t b = 0; b < n_blocks; ++b)
         if (widths[b] > type_bits) return FL_ERR_WIDTH;   // bitpacking.rs:93 unreachable!()
     fl_mixed_plan* p = new (std::nothrow) fl_mixed_plan;
@@ -850,6 +656,11 @@ int fl_mixed_plan_create(unsigned type_bits, const uint8_t* widths, size_t n_blo
     return FL_OK;
 }
 
+size_t fl_mixed_plan_n_blocks(const fl_mixed_plan* p) { return p ? p->n_blocks : 0; }
+uint64_t fl_mixed_plan_packed_bytes(const fl_mixed_plan* p) { return p ? p->packed_bytes : 0; }
+const uint64_t* fl_mixed_plan_offsets(const fl_mixed_plan* p) { return p ? p->d_offsets : nullptr; }
+const uint8_t* fl_mixed_plan_widths(const fl_mixed_plan* p) { return p ? p->d_widths : nullptr; }
+
 int fl_fill_random(void* dst, size_t n_bytes, uint64_t seed, void* stream)
 {
     if (n_bytes == 0) return FL_OK;
@@ -859,119 +670,7 @@ int fl_fill_random(void* dst, size_t n_bytes, uint64_t seed, void* stream)
     return hip_status(launch_fill_random(static_cast<uint64_t*>(dst), n_bytes / 8, seed, static_cast<hipStream_t>(stream)));
 }
 
-// ---- the bare stream (fl_stream.hpp) and the launch shape the library gives an op -----------------------------------------------
-int fl_internal_bare_stream(const void* in, size_t in_unit, const void* aux, size_t aux_unit, void* out, size_t out_unit, size_t n_units,
-                            int nt_loads, int waves, int window_log2_units, void* stream)
-{
-    if (n_units == 0) return FL_OK;
-    if ((in_unit && !in) || (aux_unit && !aux) || !out) return FL_ERR_NULL;
-    if (misaligned(in) || misaligned(aux) || misaligned(out)) return FL_ERR_ALIGN;
-    if (in_unit > BARE_MAX_UNIT || out_unit > BARE_MAX_UNIT || aux_unit > 1024 || ((in_unit | out_unit | aux_unit) & 15u)) return FL_ERR_INDEX;
-    FL_DEVICE_TIER(stream, in, aux, out);
-    BareArgs a{static_cast<const char*>(in), static_cast<const char*>(aux), static_cast<char*>(out), n_units, 0,
-               (unsigned)in_unit, (unsigned)aux_unit, (unsigned)out_unit, 63u};
-    return hip_status(launch_bare_stream(a, nt_loads != 0, waves, window_log2_units, static_cast<hipStream_t>(stream)));
-}
-
-// op: 0 unpack / unfor_pack, 1 pack / for_pack, 2 undelta_pack, 3 unpack over a mixed-width column (width = the column's mean width
-// times 2, so that 16.5 can be said).  The shape a bare stream must have to shadow that call: bytes per block on either side, the
-// cache policy of the loads, waves per SIMD and tile-map window the library's own kernel for that (T, W) runs with.
-int fl_internal_bare_stream_shape(int op, unsigned type_bits, unsigned width, size_t* in_unit, size_t* aux_unit, size_t* out_unit,
-                                  int* nt_loads, int* waves, int* window_log2_units, unsigned* blocks_per_unit)
-{
-    if (type_bits != 8 && type_bits != 16 && type_bits != 32 && type_bits != 64) return FL_ERR_INDEX;
-    if (op < 0 || op > 3) return FL_ERR_INDEX;
-    if (width > (op == 3 ? 2 * type_bits : type_bits)) return FL_ERR_WIDTH;
-    if (!in_unit || !aux_unit || !out_unit || !nt_loads || !waves || !window_log2_units || !blocks_per_unit) return FL_ERR_NULL;
-    // a wavefront's unit is at least 4 KiB of unpacked values: 4 consecutive u8 blocks, 2 u16 blocks -- the library's own kernels never
-    // give a wavefront a single 1- or 2-KiB block either (8 blocks per wavefront in the cell-column kernels, 2-4 in flight in the others),
-    // and a stream that did would measure the starving wavefront, not the memory
-    const unsigned k = type_bits == 8 ? 4u : type_bits == 16 ? 2u : 1u;
-    const size_t packed = (op == 3 ? 64u * width : 128u * width) * k, unpacked = 128u * type_bits * k;
-    *blocks_per_unit = k;
-    *in_unit = op == 1 ? unpacked : packed;
-    *out_unit = op == 1 ? packed : unpacked;
-    *aux_unit = op == 2 ? 128u * k : 0;
-    const WaveOp wop = op == 1 ? WAVE_PACK : op == 2 ? WAVE_UNDELTA_PACK : WAVE_UNPACK;
-    // two blocks per wavefront: same bytes per launch, the occupancy is what the table says
-    int w = op == 3 ? mixed_waves(type_bits, false) : chosen_waves(type_bits, width, wop).waves;
-    if (w == 0) w = 8;       // a cell-column kernel gives a wavefront 8 blocks at 2-3 waves per SIMD: the one-unit-per-wavefront stream needs every slot to keep as many bytes in flight
-    *waves = w < 3 ? 3 : w;
-    *nt_loads = op == 1 || op == 3 || width >= fl::nt_read_from(type_bits);       // fl_widths.hpp: RD_AUTO; pack reads non-temporally
-    *window_log2_units = window_log2_blocks(op == 1 ? WIN_PACK : op == 2 ? WIN_UNDELTA_PACK : WIN_UNPACK, type_bits);
-    return FL_OK;
-}
-
-int fl_internal_selftune_check(int op, unsigned type_bits, unsigned width, const void* in, const void* aux, void* out, size_t n_blocks, void* stream,
-                               float* table_ms, float* best_other_ms, int* best_other_policy)
-{
-    if (!table_ms || !best_other_ms || !best_other_policy) return FL_ERR_NULL;
-    if (op < 0 || op > 2 || (type_bits != 8 && type_bits != 16 && type_bits != 32 && type_bits != 64)) return FL_ERR_INDEX;
-    if (width > type_bits) return FL_ERR_WIDTH;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto call = [&]() -> int {
-        switch (type_bits * 4 + (unsigned)op) {
-        case 8 * 4 + 0: return fl_u8_unpack(width, (const uint8_t*)in, (uint8_t*)out, n_blocks, stream);
-        case 8 * 4 + 1: return fl_u8_pack(width, (const uint8_t*)in, (uint8_t*)out, n_blocks, stream);
-        case 8 * 4 + 2: return fl_u8_undelta_pack(width, (const uint8_t*)in, (const uint8_t*)aux, (uint8_t*)out, n_blocks, stream);
-        case 16 * 4 + 0: return fl_u16_unpack(width, (const uint16_t*)in, (uint16_t*)out, n_blocks, stream);
-        case 16 * 4 + 1: return fl_u16_pack(width, (const uint16_t*)in, (uint16_t*)out, n_blocks, stream);
-        case 16 * 4 + 2: return fl_u16_undelta_pack(width, (const uint16_t*)in, (const uint16_t*)aux, (uint16_t*)out, n_blocks, stream);
-        case 32 * 4 + 0: return fl_u32_unpack(width, (const uint32_t*)in, (uint32_t*)out, n_blocks, stream);
-        case 32 * 4 + 1: return fl_u32_pack(width, (const uint32_t*)in, (uint32_t*)out, n_blocks, stream);
-        case 32 * 4 + 2: return fl_u32_undelta_pack(width, (const uint32_t*)in, (const uint32_t*)aux, (uint32_t*)out, n_blocks, stream);
-        case 64 * 4 + 0: return fl_u64_unpack(width, (const uint64_t*)in, (uint64_t*)out, n_blocks, stream);
-        case 64 * 4 + 1: return fl_u64_pack(width, (const uint64_t*)in, (uint64_t*)out, n_blocks, stream);
-        default: return fl_u64_undelta_pack(width, (const uint64_t*)in, (const uint64_t*)aux, (uint64_t*)out, n_blocks, stream);
-        }
-    };
-    const int saved = fl_internal_get_kernel_policy();
-    int rc = FL_OK;
-    auto timed = [&](int policy, float& ms) {                // median of 3 after one untimed call
-        fl_internal_set_kernel_policy(policy);
-        rc = median_ms(s, 1, 3, call, &ms);
-    };
-    *table_ms = *best_other_ms = 0.f;
-    timed(0, *table_ms);
-    *best_other_policy = 0;
-    const fl::WaveOp wop = op == 1 ? fl::WAVE_PACK : op == 2 ? fl::WAVE_UNDELTA_PACK : fl::WAVE_UNPACK;
-    const fl::WaveChoice tab = fl::wave_choice(type_bits, width, wop);
-    for (int policy : {1, 2 + 256 * 3, 2 + 256 * 4, 2 + 256 * 5, 2 + 256 * 6, 2 + 256 * 8}) {
-        if (rc != FL_OK) break;
-        if (policy == 1 && (tab.waves == 0 || !fl::cell_column_built(type_bits, width, wop))) continue;   // the table's own choice, or not built
-        if (policy != 1 && (policy >> 8) == tab.waves && !tab.two_blocks) continue;   // the table's own choice
-        float ms = 0.f;
-        timed(policy, ms);
-        if (rc == FL_OK && ms > 0.f && (*best_other_ms == 0.f || ms < *best_other_ms)) { *best_other_ms = ms; *best_other_policy = policy; }
-    }
-    fl_internal_set_kernel_policy(saved);
-    return rc;
-}
-
-void fl_mixed_plan_destroy(fl_mixed_plan* p)
-{
-    if (!p) return;
-    if (p->d_widths) (void)hipFree(p->d_widths);
-    if (p->d_offsets) (void)hipFree(p->d_offsets);
-    delete p;
-}
-size_t fl_mixed_plan_n_blocks(const fl_mixed_plan* p) { return p ? p->n_blocks : 0; }
-uint64_t fl_mixed_plan_packed_bytes(const fl_mixed_plan* p) { return p ? p->packed_bytes : 0; }
-const uint64_t* fl_mixed_plan_offsets(const fl_mixed_plan* p) { return p ? p->d_offsets : nullptr; }
-const uint8_t* fl_mixed_plan_widths(const fl_mixed_plan* p) { return p ? p->d_widths : nullptr; }
-
 void fl_host_release(void) { g_host.release(); }
-void fl_internal_set_kernel_policy(int policy)
-{
-    const int mode = policy & 0xff, waves = (policy >> 8) & 0xff, bpw = (policy >> 16) & 0xff, prefetch = (policy >> 24) & 1,
-              window = (policy >> 25) & 31;
-    const bool ok = policy >= 0 && policy < (1 << 30) && mode <= 2 && (waves == 0 || (waves >= 3 && waves <= 8)) && bpw <= 16
-                    && (mode == 2 || (waves == 0 && bpw == 0)) && (prefetch == 0 || bpw >= 2) && (window == 0 || window >= 8);
-    g_kernel_policy.store(ok ? policy : 0, std::memory_order_relaxed);
-    fl::window_override().store(ok ? window : 0, std::memory_order_relaxed);
-}
-int fl_internal_get_kernel_policy(void) { return g_kernel_policy.load(std::memory_order_relaxed); }
-uint64_t fl_internal_zero_copy_fallbacks(void) { return g_zero_copy_fallbacks.load(std::memory_order_relaxed); }
 
 #ifdef FL_ALL_CELL_COLUMN
 const char* fl_version(void) { return "fastlanes_amd 0.6.0 (gfx950; wire format of spiraldb/fastlanes 0.1.8; FULL build: every cell-column instance, for A/B sweeps)"; }
@@ -998,7 +697,7 @@ int fl_last_hip_error(void) { return g_last_hip_error; }
 
 size_t fl_packed_len(unsigned type_bits, unsigned width)
 {
-    if (type_bits != 8 && type_bits != 16 && type_bits != 32 && type_bits != 64) return 0;
+    if (!valid_type_bits(type_bits)) return 0;
     if (width > type_bits) return 0;
     return (size_t)1024 * width / type_bits;
 }
@@ -1026,10 +725,10 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
     int fl_##S##_unpack_compare(unsigned w, const T* in, int op, T k, size_t n, uint32_t* mask, void* s)  \
     { FL_DEVICE_TIER(s, in, mask); return dev_unpack_compare<T>(w, in, op, k, n, mask, s); }                                           \
     int fl_##S##_unfor_compare(unsigned w, const T* in, const T* r, size_t rs, int op, T k, size_t n, uint32_t* mask, void* s) \
-    { FL_DEVICE_TIER(s, in, r, mask); return run_unfor_compare<T>(false, w, nullptr, nullptr, in, 0, r, rs, op, k, n, mask, nullptr, s); } \
+    { FL_DEVICE_TIER(s, in, r, mask); return run_unfor_compare<T>({false, w}, in, r, rs, op, k, n, mask, nullptr, s); } \
     int fl_##S##_unfor_compare_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, int op, T k, \
                                       size_t n, uint32_t* mask, uint32_t* ef, void* s)                   \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, ef); return run_unfor_compare<T>(true, 0, w, o, pk, pb, r, rs, op, k, n, mask, ef, s); }     \
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, ef); return run_unfor_compare<T>({true, 0, w, o, pb}, pk, r, rs, op, k, n, mask, ef, s); }     \
     int fl_##S##_block_min_max(const T* in, size_t n, T* mins, T* maxs, void* s)                          \
     { FL_DEVICE_TIER(s, in, mins, maxs); return dev_block_min_max<T>(in, n, mins, maxs, s); }                                                \
     int fl_##S##_transpose(const T* in, T* out, size_t n, void* s) { FL_DEVICE_TIER(s, in, out); return dev_transpose<T>(false, in, out, n, s); } \
@@ -1080,13 +779,13 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
     { FL_DEVICE_TIER(s, w, o, pk, idx, out, ef); return dev_unpack_single_widths<T>(w, o, pk, pb, n, idx, ni, out, ef, s); }                         \
     int fl_##S##_pack_host(unsigned w, const T* in, T* out, size_t n)                                     \
     {                                                                                                     \
-        if (w > sizeof(T) * 8) return FL_ERR_WIDTH;                                                       \
+        if (over_width<T>(w)) return FL_ERR_WIDTH;                                                        \
         return host_run<T>(in, n * 1024, nullptr, 0, out, n * plen<T>(w),                                 \
                            [&](const T* di, const T*, T* d_o, void* st) { return dev_pack<T>(w, di, d_o, n, st); }); \
     }                                                                                                     \
     int fl_##S##_unpack_host(unsigned w, const T* in, T* out, size_t n)                                   \
     {                                                                                                     \
-        if (w > sizeof(T) * 8) return FL_ERR_WIDTH;                                                       \
+        if (over_width<T>(w)) return FL_ERR_WIDTH;                                                        \
         return host_run<T>(in, n * plen<T>(w), nullptr, 0, out, n * 1024,                                 \
                            [&](const T* di, const T*, T* d_o, void* st) { return dev_unpack<T>(w, di, d_o, n, st); }); \
     }                                                                                                     \
@@ -1094,13 +793,13 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
     { return host_unpack_single<T>(w, pk, n, index, value); }                                             \
     int fl_##S##_for_pack_host(unsigned w, const T* in, T reference, T* out, size_t n)                    \
     {                                                                                                     \
-        if (w > sizeof(T) * 8) return FL_ERR_WIDTH;                                                       \
+        if (over_width<T>(w)) return FL_ERR_WIDTH;                                                        \
         return host_run<T>(in, n * 1024, &reference, 1, out, n * plen<T>(w),                              \
                            [&](const T* di, const T* da, T* d_o, void* st) { return dev_for_pack<T>(w, di, da, 0, d_o, n, st); }); \
     }                                                                                                     \
     int fl_##S##_unfor_pack_host(unsigned w, const T* in, T reference, T* out, size_t n)                  \
     {                                                                                                     \
-        if (w > sizeof(T) * 8) return FL_ERR_WIDTH;                                                       \
+        if (over_width<T>(w)) return FL_ERR_WIDTH;                                                        \
         return host_run<T>(in, n * plen<T>(w), &reference, 1, out, n * 1024,                              \
                            [&](const T* di, const T* da, T* d_o, void* st) { return dev_unfor_pack<T>(w, di, da, 0, d_o, n, st); }); \
     }                                                                                                     \
@@ -1116,7 +815,7 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
     }                                                                                                     \
     int fl_##S##_undelta_pack_host(unsigned w, const T* in, const T* b, T* out, size_t n)                 \
     {                                                                                                     \
-        if (w > sizeof(T) * 8) return FL_ERR_WIDTH;                                                       \
+        if (over_width<T>(w)) return FL_ERR_WIDTH;                                                        \
         return host_run<T>(in, n * plen<T>(w), b, n * (1024 / (sizeof(T) * 8)), out, n * 1024,            \
                            [&](const T* di, const T* da, T* d_o, void* st) { return dev_undelta_pack<T>(w, di, da, d_o, n, st); }); \
     }                                                                                                     \
@@ -1134,10 +833,10 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
 #define FL_DEFINE_SELECT(T, S)                                                                            \
     int fl_##S##_unfor_select(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, const uint64_t* oo, T* out, size_t ol, \
                               size_t n, uint32_t* ef, void* s)                                            \
-    { FL_DEVICE_TIER(s, in, r, mask, oo, out, ef); return run_unfor_select<T>(false, w, nullptr, nullptr, in, 0, r, rs, mask, oo, out, ol, n, ef, s); } \
+    { FL_DEVICE_TIER(s, in, r, mask, oo, out, ef); return run_unfor_select<T>({false, w}, in, r, rs, mask, oo, out, ol, n, ef, s); } \
     int fl_##S##_unfor_select_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
                                      const uint64_t* oo, T* out, size_t ol, size_t n, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, oo, out, ef); return run_unfor_select<T>(true, 0, w, o, pk, pb, r, rs, mask, oo, out, ol, n, ef, s); }
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, oo, out, ef); return run_unfor_select<T>({true, 0, w, o, pb}, pk, r, rs, mask, oo, out, ol, n, ef, s); }
 
 FL_DEFINE_SELECT(uint8_t, u8)
 FL_DEFINE_SELECT(uint16_t, u16)
@@ -1147,10 +846,10 @@ FL_DEFINE_SELECT(uint64_t, u64)
 #define FL_DEFINE_AGGREGATE(T, S)                                                                         \
     int fl_##S##_unfor_aggregate(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, \
                                  void* s)                                                                 \
-    { FL_DEVICE_TIER(s, in, r, mask, aggs, ef); return run_unfor_aggregate<T>(false, w, nullptr, nullptr, in, 0, r, rs, mask, n, aggs, ef, s); } \
+    { FL_DEVICE_TIER(s, in, r, mask, aggs, ef); return run_unfor_aggregate<T>({false, w}, in, r, rs, mask, n, aggs, ef, s); } \
     int fl_##S##_unfor_aggregate_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
                                         size_t n, void* aggs, uint32_t* ef, void* s)                      \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, aggs, ef); return run_unfor_aggregate<T>(true, 0, w, o, pk, pb, r, rs, mask, n, aggs, ef, s); }
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, aggs, ef); return run_unfor_aggregate<T>({true, 0, w, o, pb}, pk, r, rs, mask, n, aggs, ef, s); }
 
 FL_DEFINE_AGGREGATE(uint8_t, u8)
 FL_DEFINE_AGGREGATE(uint16_t, u16)
@@ -1160,10 +859,10 @@ FL_DEFINE_AGGREGATE(uint64_t, u64)
 #define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                                 \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \
                                      uint32_t* mask, void* s)                                             \
-    { FL_DEVICE_TIER(s, in, r, mi, mask); return run_unfor_compare_range<T>(false, w, nullptr, nullptr, in, 0, r, rs, lo, hi, cb, mi, n, mask, nullptr, s); } \
+    { FL_DEVICE_TIER(s, in, r, mi, mask); return run_unfor_compare_range<T>({false, w}, in, r, rs, lo, hi, cb, mi, n, mask, nullptr, s); } \
     int fl_##S##_unfor_compare_range_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, T lo, T hi, \
                                             int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mi, mask, ef); return run_unfor_compare_range<T>(true, 0, w, o, pk, pb, r, rs, lo, hi, cb, mi, n, mask, ef, s); }
+    { FL_DEVICE_TIER(s, w, o, pk, r, mi, mask, ef); return run_unfor_compare_range<T>({true, 0, w, o, pb}, pk, r, rs, lo, hi, cb, mi, n, mask, ef, s); }
 
 FL_DEFINE_FOR_COMPARE_RANGE(uint8_t, u8)
 FL_DEFINE_FOR_COMPARE_RANGE(uint16_t, u16)
@@ -1174,5 +873,96 @@ FL_DEFINE_TYPE(uint8_t, u8)
 FL_DEFINE_TYPE(uint16_t, u16)
 FL_DEFINE_TYPE(uint32_t, u32)
 FL_DEFINE_TYPE(uint64_t, u64)
+
+
+// ---- fl_internal_*: the hooks of the tests and the A/B tools (include/fastlanes_amd_internal.h), not part of the stable ABI ----------
+void fl_internal_set_kernel_policy(int policy)
+{
+    const KernelPolicy p = policy_fields(policy);
+    const bool ok = policy >= 0 && policy < (1 << 30) && p.mode <= 2 && (p.waves == 0 || (p.waves >= 3 && p.waves <= 8)) && p.bpw <= 16
+                    && (p.mode == 2 || (p.waves == 0 && p.bpw == 0)) && (p.prefetch == 0 || p.bpw >= 2) && (p.window == 0 || p.window >= 8);
+    g_kernel_policy.store(ok ? policy : 0, std::memory_order_relaxed);
+    fl::window_override().store(ok ? p.window : 0, std::memory_order_relaxed);
+}
+int fl_internal_get_kernel_policy(void) { return g_kernel_policy.load(std::memory_order_relaxed); }
+uint64_t fl_internal_zero_copy_fallbacks(void) { return g_zero_copy_fallbacks.load(std::memory_order_relaxed); }
+
+// ---- the bare stream (fl_stream.hpp) and the launch shape the library gives an op -----------------------------------------------
+int fl_internal_bare_stream(const void* in, size_t in_unit, const void* aux, size_t aux_unit, void* out, size_t out_unit, size_t n_units,
+                            int nt_loads, int waves, int window_log2_units, void* stream)
+{
+    if (n_units == 0) return FL_OK;
+    if ((in_unit && !in) || (aux_unit && !aux) || !out) return FL_ERR_NULL;
+    if (misaligned(in) || misaligned(aux) || misaligned(out)) return FL_ERR_ALIGN;
+    if (in_unit > BARE_MAX_UNIT || out_unit > BARE_MAX_UNIT || aux_unit > 1024 || ((in_unit | out_unit | aux_unit) & 15u)) return FL_ERR_INDEX;
+    FL_DEVICE_TIER(stream, in, aux, out);
+    BareArgs a{static_cast<const char*>(in), static_cast<const char*>(aux), static_cast<char*>(out), n_units, 0,
+               (unsigned)in_unit, (unsigned)aux_unit, (unsigned)out_unit, 63u};
+    return hip_status(launch_bare_stream(a, nt_loads != 0, waves, window_log2_units, static_cast<hipStream_t>(stream)));
+}
+
+// op: 0 unpack / unfor_pack, 1 pack / for_pack, 2 undelta_pack, 3 unpack over a mixed-width column (width = the column's mean width
+// times 2, so that 16.5 can be said).  The shape a bare stream must have to shadow that call: bytes per block on either side, the
+// cache policy of the loads, waves per SIMD and tile-map window the library's own kernel for that (T, W) runs with.
+int fl_internal_bare_stream_shape(int op, unsigned type_bits, unsigned width, size_t* in_unit, size_t* aux_unit, size_t* out_unit,
+                                  int* nt_loads, int* waves, int* window_log2_units, unsigned* blocks_per_unit)
+{
+    if (!valid_type_bits(type_bits)) return FL_ERR_INDEX;
+    if (op < 0 || op > 3) return FL_ERR_INDEX;
+    if (width > (op == 3 ? 2 * type_bits : type_bits)) return FL_ERR_WIDTH;
+    if (!in_unit || !aux_unit || !out_unit || !nt_loads || !waves || !window_log2_units || !blocks_per_unit) return FL_ERR_NULL;
+    // a wavefront's unit is at least 4 KiB of unpacked values: 4 consecutive u8 blocks, 2 u16 blocks -- the library's own kernels never
+    // give a wavefront a single 1- or 2-KiB block either (8 blocks per wavefront in the cell-column kernels, 2-4 in flight in the others),
+    // and a stream that did would measure the starving wavefront, not the memory
+    const unsigned k = type_bits == 8 ? 4u : type_bits == 16 ? 2u : 1u;
+    const size_t packed = (op == 3 ? 64u * width : 128u * width) * k, unpacked = 128u * type_bits * k;
+    *blocks_per_unit = k;
+    *in_unit = op == 1 ? unpacked : packed;
+    *out_unit = op == 1 ? packed : unpacked;
+    *aux_unit = op == 2 ? 128u * k : 0;
+    // two blocks per wavefront: same bytes per launch, the occupancy is what the table says
+    int w = op == 3 ? mixed_waves(type_bits, false) : chosen_waves(type_bits, width, tool_op(op).wave).waves;
+    if (w == 0) w = 8;       // a cell-column kernel gives a wavefront 8 blocks at 2-3 waves per SIMD: the one-unit-per-wavefront stream needs every slot to keep as many bytes in flight
+    *waves = w < 3 ? 3 : w;
+    *nt_loads = op == 1 || op == 3 || width >= fl::nt_read_from(type_bits);       // fl_widths.hpp: RD_AUTO; pack reads non-temporally
+    *window_log2_units = window_log2_blocks(tool_op(op).window, type_bits);
+    return FL_OK;
+}
+
+int fl_internal_selftune_check(int op, unsigned type_bits, unsigned width, const void* in, const void* aux, void* out, size_t n_blocks, void* stream,
+                               float* table_ms, float* best_other_ms, int* best_other_policy)
+{
+    if (!table_ms || !best_other_ms || !best_other_policy) return FL_ERR_NULL;
+    if (op < 0 || op > 2 || !valid_type_bits(type_bits)) return FL_ERR_INDEX;
+    if (width > type_bits) return FL_ERR_WIDTH;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto call = [&]() -> int {
+        return type_bits == 8 ? selftune_call<uint8_t>(op, width, in, aux, out, n_blocks, stream)
+             : type_bits == 16 ? selftune_call<uint16_t>(op, width, in, aux, out, n_blocks, stream)
+             : type_bits == 32 ? selftune_call<uint32_t>(op, width, in, aux, out, n_blocks, stream)
+                               : selftune_call<uint64_t>(op, width, in, aux, out, n_blocks, stream);
+    };
+    const int saved = fl_internal_get_kernel_policy();
+    int rc = FL_OK;
+    auto timed = [&](int policy, float& ms) {                // median of 3 after one untimed call
+        fl_internal_set_kernel_policy(policy);
+        rc = median_ms(s, 1, 3, call, &ms);
+    };
+    *table_ms = *best_other_ms = 0.f;
+    timed(0, *table_ms);
+    *best_other_policy = 0;
+    const fl::WaveOp wop = tool_op(op).wave;
+    const fl::WaveChoice tab = fl::wave_choice(type_bits, width, wop);
+    for (int policy : {1, 2 + 256 * 3, 2 + 256 * 4, 2 + 256 * 5, 2 + 256 * 6, 2 + 256 * 8}) {
+        if (rc != FL_OK) break;
+        if (policy == 1 && (tab.waves == 0 || !fl::cell_column_built(type_bits, width, wop))) continue;   // the table's own choice, or not built
+        if (policy != 1 && (policy >> 8) == tab.waves && !tab.two_blocks) continue;   // the table's own choice
+        float ms = 0.f;
+        timed(policy, ms);
+        if (rc == FL_OK && ms > 0.f && (*best_other_ms == 0.f || ms < *best_other_ms)) { *best_other_ms = ms; *best_other_policy = policy; }
+    }
+    fl_internal_set_kernel_policy(saved);
+    return rc;
+}
 
 }  // extern "C"

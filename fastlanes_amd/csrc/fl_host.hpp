@@ -1,4 +1,5 @@
-// fl_host.hpp -- host-side helpers shared by the C ABI's two translation units: fl_capi.hip (the codec boundary) and fl_pair.hip
+// fl_host.hpp -- host-side helpers shared by the C ABI's two translation units: fl_capi.hip (the codec boundary, with the host tier of
+// fl_host_tier.hpp) and fl_pair.hip
 // (fl_column_pair_alloc / _free and what stands behind them).  No kernels.  FL_DEVICE_TIER also needs fl_kernels.hpp, which both include.
 #pragma once
 #include "../../include/fastlanes_amd.h"
@@ -21,6 +22,9 @@ inline int hip_fail(hipError_t e)
 inline int hip_status(hipError_t e) { return e == hipSuccess ? FL_OK : hip_fail(e); }
 
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+// the argument checks every tier words the same way; what a failure means (FL_ERR_WIDTH, FL_ERR_INDEX, a length of 0) is the caller's
+inline bool valid_type_bits(unsigned type_bits) { return type_bits == 8 || type_bits == 16 || type_bits == 32 || type_bits == 64; }
+template <typename T> bool over_width(unsigned w) { return w > sizeof(T) * 8; }
 
 // *ms = the median of `timed` runs of launch() (a status) on `s`, each between two events, after `untimed` runs; synchronous
 template <typename F> int median_ms(hipStream_t s, int untimed, int timed, F&& launch, float* ms)

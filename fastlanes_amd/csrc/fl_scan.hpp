@@ -1,6 +1,6 @@
 // fl_scan.hpp -- widths[] -> offsets[] on the device (the exclusive prefix sum a caller of
 // bitpacking.rs:109-129 keeps implicitly by advancing its packed slice by 128*W bytes per block).
-// Included by exactly one translation unit of the library (fl_capi.hip), which instantiates what it uses.
+// Included by exactly one translation unit of the library (fl_capi.hip, as fl_host_tier.hpp is), which instantiates what it uses.
 #pragma once
 #include "fl_kernels.hpp"
 #include "fl_aggregate_map.hpp"

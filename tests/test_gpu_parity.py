@@ -1989,7 +1989,7 @@ def test_interleaved_column_pair_is_constructed_from_measured_chunks(fl, oracle,
 
 def test_zero_copy_host_calls_under_load_never_fall_back(fl, oracle):
     """The host tier's small calls are zero-copy and wait for a completion word in pinned memory instead of synchronising the
-    stream (fl_capi.hip: HostCtx::wait_zero_copy): with the chip kept busy by a device-tier stream, 1500 single-block trait calls per
+    stream (fl_host_tier.hpp: HostCtx::wait_zero_copy): with the chip kept busy by a device-tier stream, 1500 single-block trait calls per
     type return exactly the oracle's bytes, and not one of them hit the 50 ms fallback (fl_internal_zero_copy_fallbacks)."""
     import threading
     import torch
