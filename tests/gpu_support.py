@@ -1,6 +1,7 @@
 """What the GPU tests share: the `fl` and `kernel_policy` fixtures (a test module takes them by import), host <-> device copies, and
 the expected-value side of the FoR mask consumers' tests -- the mixed-width column, the mask set, numpy's comparison mask and the
-per-block aggregates.  torch is imported inside the functions that need it: collecting the suite and the numpy half of this module
+per-block aggregates -- and buffers placed off the 128-byte boundary with the padded columns that go into them (placed,
+aligned_column_host).  torch is imported inside the functions that need it: collecting the suite and the numpy half of this module
 (tests/test_support_cpu.py pins it) need no GPU."""
 import numpy as np
 import pytest
@@ -85,20 +86,166 @@ def sentinel_buffer(ty, n_elems):
     return to_dev(np.full(n_elems, sentinel_of(ty), dtype=TYPES[ty][0]))
 
 
-def mixed_column_host(ty, widths, seed):
-    """(widths as uint8, int64 byte offset of every block, packed column, per-block (w, packed) for the oracle)"""
+def mixed_column_host(ty, widths, seed, pad16=None):
+    """(widths as uint8, int64 byte offset of every block, packed column, per-block (w, packed) for the oracle).
+    pad16: 16 * pad16[b] bytes of the column's own random stream lie in front of block b -- a column whose blocks start on any
+    16-byte boundary, as fl_<ty>_unpack_widths allows -- and a fifth result follows: bool per byte of the column, True in the gaps."""
     esz = tbits(ty) // 8
     widths = np.asarray(widths).astype(np.uint8)
-    off = np.concatenate([[0], np.cumsum(widths.astype(np.int64) * 128)]) // esz
-    col = values(ty, int(off[-1]), seed)
-    return widths, (off[:-1] * esz).astype(np.int64), col, [(int(w), col[off[b]:off[b + 1]]) for b, w in enumerate(widths)]
+    if pad16 is None:
+        off = np.concatenate([[0], np.cumsum(widths.astype(np.int64) * 128)]) // esz
+        col = values(ty, int(off[-1]), seed)
+        return widths, (off[:-1] * esz).astype(np.int64), col, [(int(w), col[off[b]:off[b + 1]]) for b, w in enumerate(widths)]
+    pad = np.asarray(pad16).astype(np.int64) * 16
+    assert pad.shape == widths.shape and (pad >= 0).all()
+    size = widths.astype(np.int64) * 128
+    off = np.cumsum(pad + size) - size                                          # the block's start: behind its own gap
+    col = values(ty, int(off[-1] + size[-1]) // esz if widths.size else 0, seed)
+    gaps = np.ones(col.nbytes, bool)
+    for o, s in zip(off, size):
+        gaps[o:o + s] = False
+    blocks = [(int(w), col[o // esz:(o + s) // esz]) for w, o, s in zip(widths, off, size)]
+    return widths, off.astype(np.int64), col, blocks, gaps
 
 
-def mixed_column(ty, widths, seed):
-    """(device widths, device offsets, packed column, per-block (w, packed) for the oracle)"""
+def mixed_column(ty, widths, seed, pad16=None):
+    """(device widths, device offsets, packed column, per-block (w, packed) for the oracle[, the gaps' byte map])"""
     import torch
-    widths, off, col, blocks = mixed_column_host(ty, widths, seed)
-    return torch.from_numpy(widths).cuda(), torch.from_numpy(off).cuda(), col, blocks
+    widths, off, *rest = mixed_column_host(ty, widths, seed, pad16)
+    return (torch.from_numpy(widths).cuda(), torch.from_numpy(off).cuda(), *rest)
+
+
+# ---- buffers off the 128-byte boundary (tests/test_gpu_alignment.py; the conditions they rest on: tests/test_support_cpu.py) ----
+PLACED_FRONT = 256                              # guard bytes in front of a placed payload, at least; at least as many follow it
+
+
+def policy_bpw(policy):
+    """blocks per wavefront of a kernel policy word of POLICIES / test_gpu_for_consumer_shapes.SHAPES: the cell-column kernels take
+    one, the wave-per-block kernels the count in bits 16..23 (none given: at most 4)"""
+    return 1 if policy == 1 else ((policy >> 16) & 0xFF) or 4
+
+
+def aligned_column_blocks(bpw):
+    """two full workgroups (4 wavefronts of bpw blocks), one more wavefront, and one block"""
+    return 2 * 4 * bpw + bpw + 1
+
+
+def aligned_column_spec(ty, n):
+    """(widths, pad16, seed) of THE n-block column of `ty` whose blocks start on every 16-byte residue mod 128.
+    Widths: 0 .. T in order where the column has room for them, otherwise an ascending sample of 0 .. T that keeps 0, T//2 - 1, T//2
+    and T (both sides of the 2 * W >= T switch of the read route, and the ends); then seeded random ones.  Gaps: 48 bytes in front of
+    each of the first nine blocks (the starts of the eight behind the width-0 block take all eight residues), then 0 .. 112 seeded
+    random bytes."""
+    T = tbits(ty)
+    rs = np.random.default_rng(31000 + 64 * T + n)
+    if n > T:
+        widths = np.concatenate([np.arange(T + 1), rs.integers(0, T + 1, size=n - (T + 1))])
+    else:
+        widths = np.array(sorted({0, T // 2 - 1, T // 2, T} | {int(w) for w in np.round(np.linspace(0, T, n - 4))}))
+        widths = np.concatenate([widths, rs.integers(0, T + 1, size=n - widths.size)])
+    pad16 = np.concatenate([np.full(9, 3), rs.integers(0, 8, size=n - 9)])
+    return widths.astype(np.int64), pad16.astype(np.int64), 31100 + 64 * T + n
+
+
+def aligned_column_host(ty, n):
+    widths, pad16, seed = aligned_column_spec(ty, n)
+    return mixed_column_host(ty, widths, seed, pad16)
+
+
+ALIGNED_COLUMN_BLOCKS = [aligned_column_blocks(bpw) for bpw in (1, 3, 4, 12)]    # every column length the alignment tests use
+ALIGNED_COLUMN_BASES = (16, 80)                                                   # the residues their column base is placed at
+UNIFORM_BLOCKS = 35                             # two full workgroups at 4 blocks per wavefront, and a tail of 3
+
+
+def uniform_widths(ty):
+    """both sides of the 2 * W >= T switch of the read route, and the ends"""
+    T = tbits(ty)
+    return [0, 1, T // 2 - 1, T // 2, T]
+
+
+def uniform_packed(ty, w, n=UNIFORM_BLOCKS):
+    return values(ty, n * 128 * w // (tbits(ty) // 8), 32000 + 64 * tbits(ty) + w)
+
+
+def column_seed(ty, n, base):
+    """the seed of the allocation that holds aligned_column_host(ty, n)'s column at the residue `base`"""
+    return 34000 + 8 * (64 * tbits(ty) + n) + base // 16
+
+
+def packed_seed(ty, w, residue):
+    """the seed of the allocation (its guard bytes) that holds uniform_packed(ty, w) at `residue`"""
+    return 33000 + 8 * (64 * tbits(ty) + w) + residue // 16
+
+
+def slab_layout(sizes):
+    """(start of every array, the slab's size), in bytes, for arrays sub-allocated from one slab: array a begins at the previous
+    array's end rounded up to 16, plus 16 * (a % 8) bytes of filler -- neighbours lie 0 .. 112 bytes apart"""
+    starts, pos = [], 0
+    for a, size in enumerate(sizes):
+        pos = -(-pos // 16) * 16 + 16 * (a % 8)
+        starts.append(pos)
+        pos += int(size)
+    return starts, pos
+
+
+def placed_image(payload, residue, seed, base=0):
+    """(bytes, start): the image of one allocation at address `base` whose bytes [start, start + len(payload)) are `payload` (uint8)
+    and lie at an address = residue mod 128, start >= PLACED_FRONT; seeded random bytes everywhere else, and PLACED_FRONT of them
+    behind the payload.  The bytes in front of the payload are the END of one fixed stream per seed, so what precedes the payload
+    does not depend on `base`: the CPU pins see the guard bytes the GPU run sees."""
+    assert 0 <= residue < 128
+    payload = np.ascontiguousarray(payload).view(np.uint8).reshape(-1)
+    start = PLACED_FRONT + (residue - base - PLACED_FRONT) % 128
+    noise = np.random.default_rng(seed).integers(0, 256, size=2 * (PLACED_FRONT + 128), dtype=np.uint8)
+    half = PLACED_FRONT + 128
+    return np.concatenate([noise[half - start:half], payload, noise[half:half + PLACED_FRONT]]), start
+
+
+class Placed:
+    """One raw CUDA allocation with a typed payload inside: `t` the payload's tensor, `check_guards()` that no byte outside it changed"""
+
+    def __init__(self, raw, image, start, nbytes, ty):
+        import torch
+        self.raw, self.image, self.start, self.nbytes, self.ty = raw, image, start, nbytes, ty
+        self.t = raw[start:start + nbytes].view(getattr(torch, TDT.get(ty, ty)))
+
+    def np(self):
+        """the payload as it is now, in its own dtype"""
+        now = self.raw[self.start:self.start + self.nbytes].cpu().numpy()
+        return now.view(TYPES[self.ty][0] if self.ty in TYPES else np.dtype(self.ty))
+
+    def before(self):
+        """the payload's bytes as they were written when the buffer was made (uint8)"""
+        return self.image[self.start:self.start + self.nbytes].copy()
+
+    def check_guards(self, what=None):
+        now = self.raw.cpu().numpy()
+        end = self.start + self.nbytes
+        assert np.array_equal(now[:self.start], self.image[:self.start]), (what, "bytes in front of the buffer were written")
+        assert np.array_equal(now[end:], self.image[end:]), (what, "bytes behind the buffer were written")
+
+
+def placed(array_or_nbytes, ty, residue, seed):
+    """A buffer at `residue` mod 128 inside a raw uint8 CUDA allocation of seeded random bytes (placed_image): the payload holds
+    `array_or_nbytes`' bytes, or as many random ones.  `ty`: an element type of TYS, or a dtype name ("int32", "int64") for masks,
+    slots and indices.  residue is a multiple of 16, or -- element-aligned buffers -- of the element size."""
+    import torch
+    esz = np.dtype(TDT.get(ty, ty)).itemsize
+    assert residue % esz == 0
+    if isinstance(array_or_nbytes, (int, np.integer)):
+        payload = np.random.default_rng(seed + 1).integers(0, 256, size=int(array_or_nbytes), dtype=np.uint8)
+    else:
+        payload = np.ascontiguousarray(array_or_nbytes).view(np.uint8).reshape(-1)
+    assert payload.size % esz == 0
+    raw = torch.empty(payload.size + 2 * PLACED_FRONT + 128, dtype=torch.uint8, device="cuda:0")
+    image, start = placed_image(payload, residue, seed, raw.data_ptr())
+    assert image.size <= raw.numel() and start >= PLACED_FRONT and image.size - start - payload.size >= PLACED_FRONT
+    raw = raw[:image.size]
+    raw.copy_(torch.from_numpy(image))
+    p = Placed(raw, image, start, payload.size, ty)
+    assert (raw.data_ptr() + start) % 128 == residue
+    assert payload.size == 0 or p.t.data_ptr() % 128 == residue, (p.t.data_ptr(), residue)
+    return p
 
 
 def mask_set(n, rng, full=True, with_none=False):

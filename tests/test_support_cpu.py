@@ -10,8 +10,10 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 import gpu_support as gs
+from oracle_lib import TYPES, packed_len, tbits
 
 
 def sha(a):
@@ -126,6 +128,110 @@ def test_constants():
     assert int(gs.SENTINEL) == 0xA5A5A5A5A5A5A5A5
     assert [int(gs.sentinel_of(ty)) for ty in gs.TYS] == [0xA5, 0xA5A5, 0xA5A5A5A5, 0xA5A5A5A5A5A5A5A5]
     assert [gs.sentinel_of(ty).dtype.itemsize for ty in gs.TYS] == [1, 2, 4, 8]
+
+
+# ---- the conditions tests/test_gpu_alignment.py rests on: its columns reach every 16-byte residue, and a kernel that rounded an
+# address to 128 bytes would decode something else (so those tests can fail) ----
+def decode_at(oracle, ty, w, image, pos):
+    """the oracle's unpack of the 128 * w bytes at byte `pos` of `image` (uint8)"""
+    return oracle.unpack(ty, w, image[pos:pos + 128 * w].copy().view(TYPES[ty][0]))
+
+
+@pytest.mark.parametrize("n", gs.ALIGNED_COLUMN_BLOCKS)
+@pytest.mark.parametrize("ty", gs.TYS)
+def test_aligned_columns_reach_every_residue_and_every_route(ty, n):
+    T = tbits(ty)
+    widths, off, col, blocks, gaps = gs.aligned_column_host(ty, n)
+    spec_w, pad16, _ = gs.aligned_column_spec(ty, n)
+    assert widths.size == n == off.size == len(blocks) and np.array_equal(widths, spec_w) and widths.max() <= T
+    assert (off % 16 == 0).all() and off.dtype == np.int64
+    size = widths.astype(np.int64) * 128
+    assert off[0] == 16 * pad16[0] and (off[1:] == off[:-1] + size[:-1] + 16 * pad16[1:]).all()       # in order, no overlap
+    assert off[-1] + size[-1] == col.nbytes
+    assert set((off % 128).tolist()) == set(range(0, 128, 16))
+    if n > T:
+        assert widths[:T + 1].tolist() == list(range(T + 1))
+    assert {0, T, T // 2 - 1, T // 2} <= set(widths.tolist())
+    assert 2 * (T // 2 - 1) < T <= 2 * (T // 2)
+    # the byte map: exactly the bytes no block covers, and the blocks are the column's bytes at their offsets
+    assert gaps.dtype == bool and gaps.shape == (col.nbytes,) and int(gaps.sum()) == 16 * int(pad16.sum())
+    raw = col.view(np.uint8)
+    for (w, pk), o in zip(blocks, off):
+        assert w * 128 == pk.nbytes and not gaps[o:o + pk.nbytes].any() and np.array_equal(pk.view(np.uint8), raw[o:o + pk.nbytes])
+    # wherever the column's base lies, blocks that hold bytes start on all eight residues
+    for base in gs.ALIGNED_COLUMN_BASES:
+        assert set(((off + base) % 128)[widths > 0].tolist()) == set(range(0, 128, 16)), base
+
+
+@pytest.mark.parametrize("n", gs.ALIGNED_COLUMN_BLOCKS)
+@pytest.mark.parametrize("ty", gs.TYS)
+def test_aligned_columns_decode_differently_from_a_rounded_offset(oracle, ty, n):
+    """offsets[b] rounded down or up to 128 -- inside the column, and as an address with the column at its two residues -- gives
+    another block than offsets[b] does, for every block that does not start on a 128-byte boundary"""
+    widths, off, col, blocks, _ = gs.aligned_column_host(ty, n)
+    raw = col.view(np.uint8)
+    want = [oracle.unpack(ty, w, pk) for w, pk in blocks]
+    checked = 0
+    for b, (w, o) in enumerate(zip(widths.tolist(), off.tolist())):
+        if w == 0 or o % 128 == 0:
+            continue
+        assert np.array_equal(decode_at(oracle, ty, w, raw, o), want[b])
+        for pos in (o - o % 128, o - o % 128 + 128):
+            if pos + 128 * w <= raw.size:
+                assert not np.array_equal(decode_at(oracle, ty, w, raw, pos), want[b]), (b, w, o, pos)
+                checked += 1
+    assert checked >= n
+    for base in gs.ALIGNED_COLUMN_BASES:
+        image, start = gs.placed_image(col, base, gs.column_seed(ty, n, base))
+        assert start % 128 == base and np.array_equal(image[start:start + raw.size], raw)
+        for b, (w, o) in enumerate(zip(widths.tolist(), off.tolist())):
+            at = start + o
+            if w == 0 or at % 128 == 0:
+                continue
+            for pos in (at - at % 128, at - at % 128 + 128):
+                assert pos + 128 * w <= image.size
+                assert not np.array_equal(decode_at(oracle, ty, w, image, pos), want[b]), (base, b, w, o, pos)
+
+
+@pytest.mark.parametrize("ty", gs.TYS)
+def test_placed_uniform_columns_decode_differently_from_a_rounded_base(oracle, ty):
+    """the uniform-width inputs of the alignment tests, with the guard bytes their allocation holds in front of and behind them:
+    every block decoded from the base rounded down or up to 128 differs from the block itself"""
+    T = tbits(ty)
+    n = gs.UNIFORM_BLOCKS
+    for w in gs.uniform_widths(ty) + [T // 2 + 1]:
+        if w == 0:
+            continue
+        pk = gs.uniform_packed(ty, w)
+        assert pk.size == n * packed_len(ty, w)
+        want = oracle.batch("unpack", ty, w, pk).reshape(n, 1024)
+        for residue in range(16, 128, 16):
+            image, start = gs.placed_image(pk, residue, gs.packed_seed(ty, w, residue))
+            assert start % 128 == residue and start >= gs.PLACED_FRONT and image.size - start - pk.nbytes >= gs.PLACED_FRONT
+            assert np.array_equal(image[start:start + pk.nbytes], pk.view(np.uint8))
+            for base in (start - residue, start - residue + 128):
+                for b in (0, 1, n // 2, n - 1):
+                    assert not np.array_equal(decode_at(oracle, ty, w, image, base + 128 * w * b), want[b]), (w, residue, base, b)
+
+
+def test_placed_image_is_seeded_and_keeps_its_guard_under_any_base():
+    pay = np.arange(48, dtype=np.uint8)
+    a, sa = gs.placed_image(pay, 48, 5)
+    b, sb = gs.placed_image(pay, 48, 5, base=0x7f0000000040)
+    assert sa == 256 + 48 and (0x7f0000000040 + sb) % 128 == 48 and sb >= gs.PLACED_FRONT
+    assert np.array_equal(a[sa - 256:], b[sb - 256:])                          # the same bytes around the payload
+    assert np.array_equal(a[sa:sa + 48], pay) and a.size == sa + 48 + gs.PLACED_FRONT
+    c, _ = gs.placed_image(pay, 48, 6)
+    assert not np.array_equal(a[:sa], c[:sa]) and not np.array_equal(a[sa + 48:], c[sa + 48:])
+    assert len(set(a[:sa].tolist())) > 64 and len(set(a[sa + 48:].tolist())) > 64   # neither zeros nor one sentinel
+    assert gs.policy_bpw(0) == 4 and [gs.policy_bpw(p) for p in gs.POLICIES] == [4, 1, 4, 4, 3]
+    assert gs.ALIGNED_COLUMN_BLOCKS == [10, 28, 37, 109]
+    # a slab of arrays whose sizes are multiples of 128 (packed blocks, unpacked blocks, bases): every residue, no overlap
+    sizes = [640, 0, 128, 1152, 4224, 256, 8192, 384, 128]
+    starts, total = gs.slab_layout(sizes)
+    assert starts[0] == 0 and all(s % 16 == 0 for s in starts) and {s % 128 for s in starts[:8]} == set(range(0, 128, 16))
+    assert [b - (a + n) for a, n, b in zip(starts, sizes, starts[1:])] == [16 * (i % 8) for i in range(1, 9)]
+    assert total == starts[-1] + sizes[-1]
 
 
 def test_importing_the_support_module_does_not_import_torch():
