@@ -29,7 +29,7 @@ def _ptr(*types):
     return [ctypes.POINTER(t) for t in types]
 
 
-# THE table of the C ABI: (header macro group, symbol, restype, argtypes), in header order.  A symbol with "{ty}" is declared once per
+# THE table of the C ABI: (header macro group, symbol, restype, argtypes), in header order.  A symbol with "{ty}" (or "{vty}") is declared once per
 # element type by its group's FL_DECLARE_* macro (_T in its argtypes is that type's scalar); the groups "API" (include/fastlanes_amd.h)
 # and "INTERNAL" (include/fastlanes_amd_internal.h: test / measurement hooks, not part of the stable ABI) are plain prototypes.
 # argtypes None: left unset.  Every symbol list below, and load(), is derived from it.
@@ -118,6 +118,11 @@ _SIGNATURES = (
     ("AGGREGATE", "fl_{ty}_unfor_aggregate", _I, [_U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE", "fl_{ty}_unfor_aggregate_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_REDUCE", "fl_aggregate_reduce", _I, [_P, _Z, _P, _P]),
+    # FL_DECLARE_AGGREGATE_BY (device tier): count / sum / min / max per u8 key of the rows a mask keeps, 256 slots
+    # ({vty}: the element type of the VALUE column -- the key column is always u8.  The recorded refusal matrix of
+    # tests/test_cabi_refusals_cpu.py covers the "{ty}" rows; these rows' refusals are pinned by tests/test_aggregate_by_cpu.py.)
+    ("AGGREGATE_BY", "fl_{vty}_unfor_aggregate_by", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
+    ("AGGREGATE_BY", "fl_{vty}_unfor_aggregate_by_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -129,9 +134,9 @@ def _rows(*groups):
     for every element type -- all of u8's symbols, then u16's, ... as the header's macros expand."""
     for group in groups or dict.fromkeys(g for g, *_ in _SIGNATURES):
         rows = [r for r in _SIGNATURES if r[0] == group]
-        for ty in TYPES if "{ty}" in rows[0][1] else (None,):
+        for ty in TYPES if "{ty}" in rows[0][1] or "{vty}" in rows[0][1] else (None,):
             for _, name, restype, argtypes in rows:
-                yield name.format(ty=ty), restype, argtypes and [CTYPE[ty] if a is _T else a for a in argtypes]
+                yield name.format(ty=ty, vty=ty), restype, argtypes and [CTYPE[ty] if a is _T else a for a in argtypes]
 
 
 def _symbols(*groups):
@@ -167,6 +172,11 @@ def aggregate_symbols():
     """The symbols FL_DECLARE_AGGREGATE and FL_DECLARE_AGGREGATE_REDUCE declare: for all four element types the two aggregate entry
     points, and the reduction of their per-block slots."""
     return _symbols("AGGREGATE", "AGGREGATE_REDUCE")
+
+
+def aggregate_by_symbols():
+    """The symbols FL_DECLARE_AGGREGATE_BY declares: for all four value types the two grouped-aggregate entry points."""
+    return _symbols("AGGREGATE_BY")
 
 
 _LIB = None

@@ -495,6 +495,31 @@ class FoR:
         aux, stride, _ = FoR._ref(src, ty, reference, n)
         return _aggregate_call(f"fl_{ty}_unfor_aggregate", src, n, (width, src.ptr, aux.ptr, stride), mask, block_aggs, check)
 
+    @staticmethod
+    def unfor_aggregate_by(width, packed, reference, key_width, key_packed, key_reference, mask=None, n_blocks=None, result=None, check=True):
+        """GROUP BY a u8 key: COUNT / SUM / MIN / MAX of the values FoR.unfor_pack(width, packed, reference) yields, grouped by the u8
+        keys FoR.unfor_pack(key_width, key_packed, key_reference) yields in the same rows, where `mask` (the layout unfor_compare
+        returns: a CUDA int32 tensor of 32 words per block; None: everywhere, and no mask is read) has a 1 -- without materialising
+        either column.  Returns a CUDA int64[256, 4] tensor (`result` if given, 1024 8-byte elements): row g holds, as uint64 bit
+        patterns, count, sum (wrapping mod 2^64), min, max of the kept rows whose key is g; a key that does not occur gives
+        (0, 0, 2^64 - 1, 0).  Every row is written by every call.  A block whose mask is empty is never read; a key width of 0 (a
+        column clustered by key) reads no key byte.  Deterministic.  Device tier only; no host round trip (`check` only matters for
+        the mixed-width form).  n_blocks is only needed when both widths are 0 and there is no mask."""
+        src, ksrc = _Arg(packed), _Arg(key_packed, "u8")
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_aggregate_by is device tier (pass CUDA tensors)")
+        _same_tier(src, ksrc)
+        _check_width("u8", key_width, "unfor_aggregate_by")
+        n = _uniform_blocks(src, width, "unfor_aggregate_by", n_blocks, (key_packed if key_width else None, packed_len("u8", key_width)),
+                            (mask if _is_torch(mask) else None, 32))
+        if _uniform_blocks(ksrc, key_width, "unfor_aggregate_by", n) != n:
+            raise ValueError(f"the key column does not hold the value column's {n} blocks")
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        kaux, kstride, _ = FoR._ref(ksrc, "u8", key_reference, n)
+        return _aggregate_by_call(f"fl_{ty}_unfor_aggregate_by", src, n, (width, src.ptr, aux.ptr, stride, key_width, ksrc.ptr, kaux.ptr, kstride),
+                                  mask, result, check)
+
 
 class Delta:
     """delta.rs:6-17.  `base` holds LANES = 1024/T elements per block."""
@@ -888,6 +913,41 @@ def unfor_aggregate_widths(widths, offsets, packed, references, mask=None, block
     src = _Arg(packed)
     n, lead = _widths_column("unfor_aggregate_widths", src, widths, offsets, references=references)
     return _aggregate_call(f"fl_{src.ty}_unfor_aggregate_widths", src, n, lead, mask, block_aggs, check)
+
+
+AGGREGATE_BY_GROUPS = 256                   # include/fastlanes_amd.h: one slot per possible u8 key
+
+
+def _aggregate_by_call(name, src, n, lead, mask, result, check):
+    """The part the two grouped-aggregate forms share: mask / result validation, the launch, the error flag.  `lead`: the form's own
+    leading C arguments (the value column's, then the key column's), in front of (mask, n_blocks, result, err_flag, stream)."""
+    import torch
+    m = _select_mask(src, mask, n) if mask is not None else None
+    dev = src.x.device
+    if result is None:
+        out = torch.empty((AGGREGATE_BY_GROUPS, 4), dtype=torch.int64, device=dev)
+    else:
+        out = _consumer_out(src, result, torch.int64, AGGREGATE_BY_GROUPS * 4, name[name.index("unfor"):]).view(AGGREGATE_BY_GROUPS, 4)
+    flag = _Flag(check, dev)
+    _launch(name, dev, *lead, m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
+    flag.raise_if_set(name)                 # the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113 -- of either column
+    return out
+
+
+def unfor_aggregate_by_widths(widths, offsets, packed, references, key_widths, key_offsets, key_packed, key_references, mask=None,
+                              result=None, check=True):
+    """FoR.unfor_aggregate_by over two mixed-width columns of the same block count: COUNT / SUM / MIN / MAX of the values
+    unfor_pack_widths(widths, offsets, packed, references) yields, grouped by the u8 keys unfor_pack_widths(key_widths, key_offsets,
+    key_packed, key_references) yields in the same rows, where `mask` (32 words per block, unfor_compare_widths' layout; None:
+    everywhere) has a 1.  Returns a CUDA int64[256, 4] tensor (`result` if given), row g = count, sum, min, max of key g as
+    FoR.unfor_aggregate_by does.  The per-block device checks of unfor_pack_widths run on BOTH columns: a block that fails either
+    contributes nothing; `check=True` reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    src, ksrc = _Arg(packed), _Arg(key_packed, "u8")
+    n, lead = _widths_column("unfor_aggregate_by_widths", src, widths, offsets, ksrc, references=references)
+    kn, klead = _widths_column("unfor_aggregate_by_widths", ksrc, key_widths, key_offsets, src, references=key_references)
+    if kn != n:
+        raise ValueError(f"the key column holds {kn} blocks, the value column {n}")
+    return _aggregate_by_call(f"fl_{src.ty}_unfor_aggregate_by_widths", src, n, (*lead, *klead), mask, result, check)
 
 
 def for_pack_widths(widths, offsets, input, references, output, check=True):

@@ -20,6 +20,7 @@
 #include "fl_for_compare_range.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
+#include "fl_aggregate_by.hpp"
 #include "fl_host_tier.hpp"
 
 #include <algorithm>
@@ -383,7 +384,8 @@ int run_chain_widths(int op, const uint8_t* widths, const uint64_t* offsets, con
     return rc >= 0 ? rc : hip_fail(hipErrorInvalidDeviceFunction);
 }
 
-// The four consumers of a FoR-packed column (fl_for_block.hpp): unfor_compare, unfor_compare_range, unfor_select, unfor_aggregate, each over
+// The consumers of a FoR-packed column (fl_for_block.hpp): unfor_compare, unfor_compare_range, unfor_select, unfor_aggregate (and
+// unfor_aggregate_by, which takes two of them), each over
 // a uniform-width column (col.width, blocks back to back) or a mixed-width one (widths[] / offsets[], checked per block by the kernel).
 // false: one of the column's pointers is missing (FL_ERR_NULL).  A mixed-width column whose blocks all have width 0 has no packed bytes:
 // its packed pointer may be NULL (run_widths) and is replaced here.
@@ -487,6 +489,33 @@ int run_unfor_aggregate(const Column& col, const T* packed, const T* refs, size_
     a.aggs = static_cast<char*>(block_aggs);
     a.agg_refs = refs;
     return hip_status(aggregate_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// unfor_aggregate_by (fl_aggregate_by.hpp): a value column of T and a u8 key column of the same form, both uniform or both mixed; a
+// block that fails either column's checks contributes nothing.  `result` (256 slots) is written by EVERY call -- the init launch also
+// answers an empty column -- so it is required and checked before the empty-column return.  The persistent grid takes the policy's
+// waves as its residency and the policy's blocks per wavefront as the least length of a wavefront's run (0: the column divided evenly).
+template <typename T>
+int run_unfor_aggregate_by(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const uint8_t* keys,
+                           const uint8_t* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, void* result,
+                           uint32_t* err_flag, void* stream)
+{
+    if ((!col.mixed && over_width<T>(col.width)) || (!kcol.mixed && over_width<uint8_t>(kcol.width))) return FL_ERR_WIDTH;
+    if (!result) return FL_ERR_NULL;
+    if (n_blocks && (!block_consumer_column(col, packed, refs) || !block_consumer_column(kcol, keys, key_refs))) return FL_ERR_NULL;
+    if ((n_blocks && (misaligned(packed) || misaligned(keys) || misaligned(mask))) || misaligned(result)) return FL_ERR_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipError_t e = launch_aggregate_by_init(static_cast<BlockAggregate*>(result), s); e != hipSuccess || n_blocks == 0) return hip_status(e);
+    const WaveShape sh = with_policy({0, 0u, 0u});
+    AggregateByArgs a;
+    widths_args<T>(a.val, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    widths_args<uint8_t>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    a.val_refs = refs;
+    a.key_refs = key_refs;
+    a.mask = mask;
+    a.result = static_cast<BlockAggregate*>(result);
+    a.run = 0;
+    return hip_status(aggregate_by_launcher<T>()(a, sh.waves, s));
 }
 
 template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n, uint8_t* widths, void* s)
@@ -855,6 +884,26 @@ FL_DEFINE_AGGREGATE(uint8_t, u8)
 FL_DEFINE_AGGREGATE(uint16_t, u16)
 FL_DEFINE_AGGREGATE(uint32_t, u32)
 FL_DEFINE_AGGREGATE(uint64_t, u64)
+
+#define FL_DEFINE_AGGREGATE_BY(T, S)                                                                      \
+    int fl_##S##_unfor_aggregate_by(unsigned w, const T* in, const T* r, size_t rs, unsigned kw, const uint8_t* k, const uint8_t* kr, size_t krs, \
+                                    const uint32_t* mask, size_t n, void* res, uint32_t* ef, void* s)     \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, in, r, k, kr, mask, res, ef);                                                   \
+        return run_unfor_aggregate_by<T>({false, w}, in, r, rs, {false, kw}, k, kr, krs, mask, n, res, ef, s); \
+    }                                                                                                     \
+    int fl_##S##_unfor_aggregate_by_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint8_t* kw, \
+                                           const uint64_t* ko, const uint8_t* k, size_t kb, const uint8_t* kr, size_t krs, const uint32_t* mask, \
+                                           size_t n, void* res, uint32_t* ef, void* s)                    \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, w, o, pk, r, kw, ko, k, kr, mask, res, ef);                                     \
+        return run_unfor_aggregate_by<T>({true, 0, w, o, pb}, pk, r, rs, {true, 0, kw, ko, kb}, k, kr, krs, mask, n, res, ef, s); \
+    }
+
+FL_DEFINE_AGGREGATE_BY(uint8_t, u8)
+FL_DEFINE_AGGREGATE_BY(uint16_t, u16)
+FL_DEFINE_AGGREGATE_BY(uint32_t, u32)
+FL_DEFINE_AGGREGATE_BY(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                                 \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \

@@ -10,6 +10,7 @@
 //   14 unfor_select (only the rows a selection mask keeps, from the same columns; fl_select.hpp)
 //   15 unfor_aggregate (count / sum / min / max per block of the rows a mask keeps, from the same columns; fl_aggregate.hpp)
 //   16 unfor_compare_range (interval predicates over the same columns, chained through the mask so far; fl_for_compare_range.hpp)
+//   17 unfor_aggregate_by (count / sum / min / max per u8 key of the rows a mask keeps, value and key column both FoR-packed; fl_aggregate_by.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -20,6 +21,7 @@
 #include "fl_for_compare_range.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
+#include "fl_aggregate_by.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -132,7 +134,9 @@ template <> select_launch_t select_launcher<T>() { return &launch_block_consumer
 template <> aggregate_launch_t aggregate_launcher<T>() { return &launch_block_consumer<T, AggregateArgs, k_unfor_aggregate<T>, true>; }
 #elif FL_FAMILY == 16
 template <> for_range_launch_t for_range_launcher<T>() { return &launch_block_consumer<T, ForRangeArgs, k_unfor_compare_range<T>, false>; }
+#elif FL_FAMILY == 17
+template <> aggregate_by_launch_t aggregate_by_launcher<T>() { return &launch_aggregate_by<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..16"
+#error "FL_FAMILY must be 0..6 or 8..17"
 #endif
 }  // namespace fl

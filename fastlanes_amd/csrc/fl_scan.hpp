@@ -230,6 +230,18 @@ inline hipError_t launch_aggregate_reduce(const BlockAggregate* slots, uint64_t 
     return hipGetLastError();
 }
 
+// unfor_aggregate_by's init launch (fl_aggregate_by.hpp): the 256 identities its wavefronts then fold their tables into, on the same
+// stream in front of them -- the shape of k_aggregate_init above.  Also the whole answer of an empty column.
+__global__ __launch_bounds__(256) void k_aggregate_by_init(BlockAggregate* result)     // one thread per group
+{
+    result[threadIdx.x] = aggregate_identity();
+}
+inline hipError_t launch_aggregate_by_init(BlockAggregate* result, hipStream_t s)
+{
+    FL_LAUNCH(k_aggregate_by_init, dim3(1), dim3(256), 0, s, result);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // An encoder's width choice for FoR with reference = the block's minimum (ffor.rs:24-36 packs `in[idx] - reference`, masked to
 // W bits by macros.rs:73): widths[b] = number of bits of maxs[b] - mins[b] (0 when the block is constant) is the smallest W that

@@ -523,6 +523,52 @@ FL_DECLARE_AGGREGATE(uint64_t, u64)
     int fl_##NAME(const void *block_aggs, size_t n_blocks, void *result, void *stream);
 FL_DECLARE_AGGREGATE_REDUCE(aggregate_reduce)
 
+/*
+ * EXTENSION (GROUP BY on top of the aggregate above): COUNT / SUM / MIN / MAX of a FoR-packed VALUE column of type T grouped by a
+ * FoR-packed KEY column of type u8 with the same n_blocks, over the rows a selection mask keeps -- SELECT k, COUNT(*), SUM(y), MIN(y),
+ * MAX(y) WHERE <mask> GROUP BY k -- without materialising either column.  Both columns are uniform width (the first form) or both
+ * mixed width (the _widths form); the mask has the layout the compare entry points write (32 uint32 words per block, bit i of block b
+ * = bit i % 32 of word b*32 + i/32).  As a composition of reference functions:
+ *     val_b[i] = unfor_pack::<W_b >(value block b, references    [b * reference_stride    ])[i]                       (ffor.rs:38-50)
+ *     key_b[i] = unfor_pack::<KW_b>(key   block b, key_references[b * key_reference_stride])[i]                (u8, wrapping add)
+ *     result[g] = combine over all (b, i) with mask bit (b, i) set and key_b[i] == g of {1, val, val, val}
+ * with val = val_b[i] zero-extended to uint64, and combine and the identity {0, 0, UINT64_MAX, 0} exactly those of fl_block_aggregate
+ * above.  `result` is ALWAYS 256 slots (a device array of 256 fl_block_aggregate, 8 KiB), one per possible u8 key: there is no
+ * n_groups argument, so a key can never be out of range.  Every slot is written by every call; a group that does not occur, and every
+ * group when n_blocks == 0, receives the identity.  mask == NULL keeps every row, and no mask is read; a reference stride of 0
+ * broadcasts references[0] / key_references[0].  Integer add, min and max are associative and commutative: the result is
+ * deterministic.  Asynchronous on `stream`, no allocation, no synchronisation, no scratch memory: a small launch writes the 256
+ * identities, the kernel behind it folds its wavefronts' tables into them with 64-bit atomics.
+ * A block whose mask is empty is never read; a key block of width 0 (a column sorted or clustered by key) is answered from its
+ * reference, no key byte is read, and its value block is aggregated exactly as fl_<ty>_unfor_aggregate does (a value width of 0 reads
+ * nothing at all).  The mixed-width form runs the per-block device checks of fl_<ty>_unfor_pack_widths on BOTH columns: a block that
+ * fails either check raises its FL_DEVERR_* bit in *err_flag and contributes NOTHING; neither of its columns is read.
+ * width > T or key_width > 8 is FL_ERR_WIDTH (also for an empty column); `result` is required by every call, the other pointers when
+ * n_blocks > 0 (FL_ERR_NULL) -- `in` / `packed` / `keys` may be NULL only when no byte of it can be read (width 0, or its packed
+ * bytes == 0); `in` / `packed`, `keys`, `mask` and `result` are 16-byte aligned (FL_ERR_ALIGN).
+ * Out of scope: keys wider than u8 (a hash group-by), Delta columns, several value columns per launch, and the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list and the list of other functions are pinned surfaces.)
+ */
+#define FL_DECLARE_AGGREGATE_BY(T, S)                                                                     \
+    int fl_##S##_unfor_aggregate_by(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                    unsigned key_width, const uint8_t *keys, const uint8_t *key_references, \
+                                    size_t key_reference_stride, const uint32_t *mask /* may be NULL */,  \
+                                    size_t n_blocks, void *result /* fl_block_aggregate[256] */,          \
+                                    uint32_t *err_flag, void *stream);                                    \
+    int fl_##S##_unfor_aggregate_by_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                           size_t packed_bytes, const T *references, size_t reference_stride, \
+                                           const uint8_t *key_widths, const uint64_t *key_offsets,        \
+                                           const uint8_t *keys, size_t keys_bytes,                        \
+                                           const uint8_t *key_references, size_t key_reference_stride,    \
+                                           const uint32_t *mask /* may be NULL */, size_t n_blocks,       \
+                                           void *result /* fl_block_aggregate[256] */,                    \
+                                           uint32_t *err_flag, void *stream);
+
+FL_DECLARE_AGGREGATE_BY(uint8_t, u8)
+FL_DECLARE_AGGREGATE_BY(uint16_t, u16)
+FL_DECLARE_AGGREGATE_BY(uint32_t, u32)
+FL_DECLARE_AGGREGATE_BY(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

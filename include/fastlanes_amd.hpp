@@ -67,6 +67,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_select_widths = fl_##S##_unfor_select_widths;                    \
         static constexpr auto unfor_aggregate = fl_##S##_unfor_aggregate;                            \
         static constexpr auto unfor_aggregate_widths = fl_##S##_unfor_aggregate_widths;              \
+        static constexpr auto unfor_aggregate_by = fl_##S##_unfor_aggregate_by;                      \
+        static constexpr auto unfor_aggregate_by_widths = fl_##S##_unfor_aggregate_by_widths;        \
         static constexpr auto unpack_mixed = fl_##S##_unpack_mixed;                                  \
         static constexpr auto pack_mixed = fl_##S##_pack_mixed;                                      \
         static constexpr auto unpack_widths = fl_##S##_unpack_widths;                                \
@@ -214,6 +216,13 @@ template <typename T> struct FoR : BitPacking<T> {
                                        std::size_t n_blocks, fl_block_aggregate* d_block_aggs, std::uint32_t* d_err_flag = nullptr,
                                        void* stream = nullptr)
     { detail::check(A::unfor_aggregate((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_device"); }
+    // the same grouped by a FoR-packed u8 key column of the same block count: d_result[g], g = 0 .. 255, = count / sum / min / max of the
+    // kept rows whose key is g (the identity where there are none); all 256 slots are written by every call
+    static void unfor_aggregate_by_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, std::size_t key_width,
+                                          const std::uint8_t* d_keys, const std::uint8_t* d_key_refs, std::size_t key_ref_stride,
+                                          const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_result,
+                                          std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_aggregate_by((unsigned)width, d_packed, d_refs, ref_stride, (unsigned)key_width, d_keys, d_key_refs, key_ref_stride, d_mask, n_blocks, d_result, d_err_flag, stream), "unfor_aggregate_by_device"); }
 };
 
 // delta.rs:6-17
@@ -463,6 +472,15 @@ inline void unfor_aggregate_widths_device(const std::uint8_t* d_widths, const st
                                           const T* d_references, std::size_t reference_stride, const std::uint32_t* d_mask, std::size_t n_blocks,
                                           fl_block_aggregate* d_block_aggs, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_aggregate_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_widths"); }
+// unfor_aggregate_by over two mixed-width columns (value: T, key: u8) of the same block count; both columns get unfor_pack_widths' device
+// checks, a block that fails either contributes nothing
+template <typename T>
+inline void unfor_aggregate_by_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                             const T* d_references, std::size_t reference_stride, const std::uint8_t* d_key_widths,
+                                             const std::uint64_t* d_key_offsets, const std::uint8_t* d_keys, std::size_t keys_bytes,
+                                             const std::uint8_t* d_key_references, std::size_t key_reference_stride, const std::uint32_t* d_mask,
+                                             std::size_t n_blocks, fl_block_aggregate* d_result, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_aggregate_by_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_key_widths, d_key_offsets, d_keys, keys_bytes, d_key_references, key_reference_stride, d_mask, n_blocks, d_result, d_err_flag, stream), "unfor_aggregate_by_widths"); }
 // per-block aggregates -> the column's: counts and sums added (wrapping), the smallest min, the largest max; no blocks: the identity
 inline void aggregate_reduce_device(const fl_block_aggregate* d_block_aggs, std::size_t n_blocks, fl_block_aggregate* d_result, void* stream = nullptr)
 { detail::check(fl_aggregate_reduce(d_block_aggs, n_blocks, d_result, stream), "aggregate_reduce"); }

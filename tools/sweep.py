@@ -876,6 +876,115 @@ def main():
         ms = round_robin({"aggregate_reduce": lambda: fl.aggregate_reduce(slots)})
         print(f"aggregate_reduce {n} blocks  {show(ms['aggregate_reduce'])}  {n * 32 / sorted(ms['aggregate_reduce'])[reps // 2] / 1e6:8.1f} GB/s", flush=True)
         return
+    if args.cases == "aggregate_by":
+        # unfor_aggregate_by_widths (count / sum / min / max per u8 key under a selection mask) over the mixed-width column of --cases mixed
+        # with a u8 key column beside it: 4 groups uniform (key width 2), 256 groups uniform (key width 8), clustered (every key block
+        # width 0); mask 100 %, 1 % and none.  Two comparison rows are timed in the SAME run on the SAME buffers, round-robin with the row
+        # under test: (a) unfor_aggregate_widths of the value column plus unfor_pack_widths of the key column -- the same bytes read, no
+        # grouping; (b) the composition the call replaces: unfor_pack_widths of both columns, then torch bincount / scatter_add /
+        # scatter_reduce over the decoded rows (the mask already expanded to a bool tensor, outside the timing).  Every figure is the
+        # median of `reps` launches with their min .. max beside it; the device's unique id heads the table.
+        reps = max(args.reps, 5)
+        props = torch.cuda.get_device_properties(dev)
+        print(f"# device {props.name} unique id {getattr(props, 'uuid', 'unknown')}", flush=True)
+
+        def round_robin(variants):
+            """{name: [ms, ...]}: `reps` timed launches of every variant, interleaved, after two untimed rounds"""
+            for _ in range(2):
+                for f in variants.values():
+                    f()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in variants}
+            for _ in range(reps):
+                for k, f in variants.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); f(); b.record(); b.synchronize()
+                    ms[k].append(a.elapsed_time(b))
+            return ms
+
+        def random_bits(n, density, seed):
+            g = torch.Generator(device=dev); g.manual_seed(seed)
+            if density >= 1.0:
+                return torch.ones(n * 1024, dtype=torch.bool, device=dev)
+            return torch.rand(n * 1024, device=dev, generator=g) < density
+
+        def words_of(bits):
+            """int32 words of a bool mask, built 32 Ki blocks at a time"""
+            out = torch.empty(bits.numel() // 32, dtype=torch.int32, device=dev)
+            sh = torch.arange(32, device=dev)
+            step = 32768 * 1024
+            for i in range(0, bits.numel(), step):
+                w64 = (bits[i:i + step].view(-1, 32).to(torch.int64) << sh).sum(dim=1)
+                out[i // 32:i // 32 + w64.numel()] = torch.where(w64 >= 1 << 31, w64 - (1 << 32), w64).to(torch.int32)
+            return out
+
+        def show(ms):
+            v = sorted(ms)
+            return f"{v[len(v) // 2]:9.4f} ms ({v[0]:.4f} .. {v[-1]:.4f})"
+
+        SIGNED = {"u8": torch.uint8, "u16": torch.int16, "u32": torch.int32, "u64": torch.int64}
+        for ty in ("u32", "u64", "u16", "u8"):
+            if args.types and ty not in args.types.split(","):
+                continue
+            T, esz = ESZ[ty] * 8, ESZ[ty]
+            n = max(64, int(args.gb * 1e9 / (128 * T * 1.5)))
+            g = torch.Generator(device=dev); g.manual_seed(31 + T)
+            widths = torch.randint(1, T, (n,), dtype=torch.int64, device=dev, generator=g).to(torch.uint8)
+            offsets, total = fl.widths_to_offsets(ty, widths)
+            pbytes = int(total.item())
+            col = rnd(pbytes, 1).view(TDT[ty])
+            refs = rnd(n * 8, 2).view(torch.uint8).view(-1, 8)[:, :esz].contiguous().view(TDT[ty]).reshape(-1)
+            un = torch.empty(n * 1024, dtype=TDT[ty], device=dev)
+            kun = torch.empty(n * 1024, dtype=torch.uint8, device=dev)
+            slots = torch.empty((n, 4), dtype=torch.int64, device=dev)
+            result = torch.empty((256, 4), dtype=torch.int64, device=dev)
+            krefs_clustered = rnd((n + 7) // 8 * 8, 3).view(torch.uint8)[:n].contiguous()
+            kzero = torch.zeros(1, dtype=torch.uint8, device=dev)
+            print(f"# {ty}: n = {n} blocks, packed values {pbytes / 1e9:.2f} GB ({pbytes / n:.1f} B/block), {reps} launches each, round-robin", flush=True)
+            for kname, kwidth, krefs in (("4 groups", 2, kzero), ("256 groups", 8, kzero), ("clustered", 0, krefs_clustered)):
+                kwidths = torch.full((n,), kwidth, dtype=torch.uint8, device=dev)
+                koffsets, ktotal = fl.widths_to_offsets("u8", kwidths)
+                kbytes = int(ktotal.item())
+                kcol = rnd(max(kbytes, 16), 4).view(torch.uint8)[:kbytes]
+                for mname, density in (("100 %", 1.0), ("1 %", 0.01), ("mask=None", None)):
+                    bits = None if density is None else random_bits(n, density, 77 + T)
+                    mask = None if bits is None else words_of(bits)
+
+                    def composition():
+                        v = fl.unfor_pack_widths(widths, offsets, col, refs, output=un, check=False).view(SIGNED[ty]).to(torch.int64)
+                        k = fl.unfor_pack_widths(kwidths, koffsets, kcol, krefs, output=kun, check=False).to(torch.int64)
+                        if T < 64:
+                            v &= (1 << T) - 1
+                        if bits is not None and density < 1.0:
+                            v, k = v[bits], k[bits]
+                        count = torch.bincount(k, minlength=256)
+                        total_ = torch.zeros(256, dtype=torch.int64, device=dev).scatter_add_(0, k, v)
+                        lo = torch.full((256,), (1 << 63) - 1, dtype=torch.int64, device=dev).scatter_reduce_(0, k, v, "amin")
+                        hi = torch.full((256,), -(1 << 63), dtype=torch.int64, device=dev).scatter_reduce_(0, k, v, "amax")
+                        return count, total_, lo, hi
+
+                    def ungrouped():
+                        fl.unfor_aggregate_widths(widths, offsets, col, refs, mask, block_aggs=slots, check=False)
+                        fl.unfor_pack_widths(kwidths, koffsets, kcol, krefs, output=kun, check=False)
+
+                    variants = {
+                        "aggregate_by": lambda: fl.unfor_aggregate_by_widths(widths, offsets, col, refs, kwidths, koffsets, kcol, krefs, mask,
+                                                                             result=result, check=False),
+                        "(a) aggregate + key unpack": ungrouped,
+                        "(b) unpack both + torch": composition,
+                    }
+                    ms = round_robin(variants)
+                    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+                    by = med["aggregate_by"]
+                    print(f"unfor_aggregate_by_widths {ty:4s} keys {kname:10s} mask {mname:9s}  {show(ms['aggregate_by'])}  {n / by / 1e6:8.3f} Gblocks/s", flush=True)
+                    for k in variants:
+                        if k != "aggregate_by":
+                            print(f"    {k:28s} {ty:4s} {show(ms[k])}  {n / med[k] / 1e6:8.3f} Gblocks/s  aggregate_by x{by / med[k]:.3f} of it", flush=True)
+                    del bits, mask, variants
+                del kwidths, koffsets, kcol
+            del col, un, kun, refs, slots
+            torch.cuda.empty_cache()
+        return
     if args.cases == "compare_range":
         # unfor_compare_range_widths (an interval predicate chained through a mask) over the mixed-width column of --cases mixed, under the
         # UNDECIDED predicate of that case (every block's value range straddles the constant, so no block is answered from its metadata and
