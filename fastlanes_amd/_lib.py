@@ -123,6 +123,10 @@ _SIGNATURES = (
     # tests/test_cabi_refusals_cpu.py covers the "{ty}" rows; these rows' refusals are pinned by tests/test_aggregate_by_cpu.py.)
     ("AGGREGATE_BY", "fl_{vty}_unfor_aggregate_by", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_BY", "fl_{vty}_unfor_aggregate_by_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_FOR_COMPARE_COLUMNS (device tier): a <op> b between two FoR-packed columns of one element type, chained through a mask
+    # ({vty} as above: these rows' refusals are pinned by tests/test_for_compare_columns_cpu.py)
+    ("FOR_COMPARE_COLUMNS", "fl_{vty}_unfor_compare_columns", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _P]),
+    ("FOR_COMPARE_COLUMNS", "fl_{vty}_unfor_compare_columns_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _I, _I, _I, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -177,6 +181,11 @@ def aggregate_symbols():
 def aggregate_by_symbols():
     """The symbols FL_DECLARE_AGGREGATE_BY declares: for all four value types the two grouped-aggregate entry points."""
     return _symbols("AGGREGATE_BY")
+
+
+def for_compare_columns_symbols():
+    """The symbols FL_DECLARE_FOR_COMPARE_COLUMNS declares: for all four element types the two column-against-column entry points."""
+    return _symbols("FOR_COMPARE_COLUMNS")
 
 
 _LIB = None

@@ -462,6 +462,39 @@ class FoR:
         return out
 
     @staticmethod
+    def unfor_compare_columns(width_a, a, a_reference, op, width_b, b, b_reference, *, signed=False, mask=None, combine="new", n_blocks=None,
+                              output=None):
+        """A predicate between two columns, chained through a mask: with va = FoR.unfor_pack(width_a, a block, a_reference)[i] and vb
+        the same of column `b` (the same element type and block count; the widths may differ), hit = va <op> vb, op in '==', '!=',
+        '<', '<=', '>', '>=' -- unsigned, or with signed=True of the two's-complement values.  combine "new": the result is hit
+        (`mask` is ignored); "and" / "or": `mask` & hit / `mask` | hit, `mask` a CUDA int32 tensor of 32 words per block (the layout
+        unfor_compare returns).  A block pair its references and widths decide, a block whose `mask` is all zero under "and", and one
+        whose `mask` is all ones under "or" are answered without reading either column; a column of width 0 is never read.  `output`
+        may be `mask` itself (in place).  Device tier only; returns a CUDA int32 tensor of 32 words per block (`output` if given).
+        n_blocks is only needed when both widths are 0 and there is neither a mask nor an output."""
+        import torch
+        cb = _range_combine(combine, mask)
+        sa, sb = _Arg(a), _Arg(b)
+        ty = sa.ty
+        if not sa.torch:
+            raise TypeError("unfor_compare_columns is device tier (pass CUDA tensors)")
+        if sb.ty != ty:
+            raise TypeError(f"both columns must have one element type, got {ty} and {sb.ty}")
+        _same_tier(sa, sb)
+        _check_width(ty, width_b, "unfor_compare_columns")
+        n = _uniform_blocks(sa, width_a, "unfor_compare_columns", n_blocks, (b if width_b else None, packed_len(ty, width_b)),
+                            (mask if cb and _is_torch(mask) else None, 32), (output, 32))
+        if _uniform_blocks(sb, width_b, "unfor_compare_columns", n) != n:
+            raise ValueError(f"column b does not hold column a's {n} blocks")
+        m = _select_mask(sa, mask, n) if cb else None
+        out = _consumer_out(sa, output, torch.int32, n * 32, "unfor_compare_columns")
+        ra, stride_a, _ = FoR._ref(sa, ty, a_reference, n)
+        rb, stride_b, _ = FoR._ref(sb, ty, b_reference, n)
+        _launch(f"fl_{ty}_unfor_compare_columns", sa.x.device, width_a, sa.ptr, ra.ptr, stride_a, width_b, sb.ptr, rb.ptr, stride_b,
+                BitPacking.CMP[op], int(bool(signed)), cb, m.ptr if m is not None and n else None, n, out.data_ptr())
+        return out
+
+    @staticmethod
     def unfor_select(width, packed, reference, mask, out_offsets=None, total=None, n_blocks=None, output=None, check=True):
         """Only the rows a selection mask keeps: the values FoR.unfor_pack(width, packed, reference) yields where `mask` (the layout
         unfor_compare returns: a CUDA int32 tensor of 32 words per block, bit i of word i//32, LSB first) has a 1, compacted, in
@@ -816,6 +849,37 @@ def unfor_compare_range_widths(widths, offsets, packed, references, lo, hi, mask
     _launch(f"fl_{ty}_unfor_compare_range_widths", src.x.device, *lead, _scalar(ty, lo), _scalar(ty, hi), cb,
             m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_unfor_compare_range_widths")    # bitpacking.rs:93,126 unreachable!(); :111-113
+    return out
+
+
+def unfor_compare_columns_widths(a_widths, a_offsets, a_packed, a_references, op, b_widths, b_offsets, b_packed, b_references, *,
+                                 signed=False, mask=None, combine="new", output=None, check=True):
+    """FoR.unfor_compare_columns over two mixed-width columns of the same element type and block count: va <op> vb of the values
+    unfor_pack_widths yields for column a and for column b in the same rows (signed=True: of the two's-complement values), joined
+    with the mask so far -- combine "new": the hits themselves (`mask` is ignored), "and" / "or": `mask` & hits / `mask` | hits.
+    `mask` and the result are CUDA int32 tensors of 32 words per block (unfor_compare_widths' layout); `output` may be `mask` itself
+    (in place).  A block pair its references and widths decide, a block whose `mask` is all zero under "and", and one whose `mask`
+    is all ones under "or" are answered without reading either column; a block of width 0 is never read.  The per-block device
+    checks of unfor_pack_widths run on BOTH columns: a block that fails either is skipped (its 32 mask words are left as they were,
+    neither column is read); `check=True` reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    import torch
+    cb = _range_combine(combine, mask)
+    if cb and _is_torch(mask) and _is_torch(a_widths) and mask.numel() != 32 * a_widths.numel():
+        raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block = {32 * a_widths.numel()}")
+    sa, sb = _Arg(a_packed), _Arg(b_packed)
+    ty = sa.ty
+    if sb.ty != ty:
+        raise TypeError(f"both columns must have one element type, got {ty} and {sb.ty}")
+    n, lead_a = _widths_column("unfor_compare_columns_widths", sa, a_widths, a_offsets, sb, references=a_references)
+    nb, lead_b = _widths_column("unfor_compare_columns_widths", sb, b_widths, b_offsets, sa, references=b_references)
+    if nb != n:
+        raise ValueError(f"column b holds {nb} blocks, column a {n}")
+    m = _select_mask(sa, mask, n) if cb else None
+    out = _consumer_out(sa, output, torch.int32, n * 32, "unfor_compare_columns_widths")
+    flag = _Flag(check, sa.x.device)
+    _launch(f"fl_{ty}_unfor_compare_columns_widths", sa.x.device, *lead_a, *lead_b, BitPacking.CMP[op], int(bool(signed)), cb,
+            m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_compare_columns_widths")  # bitpacking.rs:93,126 unreachable!(); :111-113 -- of either column
     return out
 
 

@@ -21,6 +21,7 @@
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
+#include "fl_for_compare_columns.hpp"
 #include "fl_host_tier.hpp"
 
 #include <algorithm>
@@ -448,6 +449,42 @@ int run_unfor_compare_range(const Column& col, const T* packed, const T* refs, s
     a.mask_in = reinterpret_cast<const char*>(mask_in);
     a.combine = (unsigned)combine;
     return hip_status(for_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// unfor_compare_columns (fl_for_compare_columns.hpp): two columns of T of the same form, both uniform or both mixed.  The six ops become
+// one base relation, "swap the columns" and "invert" here, once per call (fl_columns_decide.hpp: columns_relation); the swap is done
+// here, so the kernel's column a is always the base relation's left side.  The launch shape and the order of the checks are those of
+// run_unfor_compare_range; `mask` may be `mask_in`.
+template <typename T>
+int run_unfor_compare_columns(const Column& cola, const T* a_packed, const T* a_refs, size_t a_ref_stride, const Column& colb, const T* b_packed,
+                              const T* b_refs, size_t b_ref_stride, int op, int is_signed, int combine, const uint32_t* mask_in,
+                              size_t n_blocks, uint32_t* mask, uint32_t* err_flag, void* stream)
+{
+    if ((!cola.mixed && over_width<T>(cola.width)) || (!colb.mixed && over_width<T>(colb.width))) return FL_ERR_WIDTH;
+    if (op < FL_CMP_EQ || op > FL_CMP_GE || combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
+    else if (!mask_in) return FL_ERR_NULL;
+    if (!block_consumer_column(cola, a_packed, a_refs) || !block_consumer_column(colb, b_packed, b_refs) || !mask) return FL_ERR_NULL;
+    if (misaligned(a_packed) || misaligned(b_packed) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
+    const ColumnsRelation rel = columns_relation(op);
+    ForColumnsArgs a;
+    uint32_t* ef = cola.mixed ? err_flag : nullptr;
+    const WaveShape sh = rel.swap ? block_consumer_args<T>(a, colb, b_packed, b_ref_stride, n_blocks, ef)
+                                  : block_consumer_args<T>(a, cola, a_packed, a_ref_stride, n_blocks, ef);
+    if (rel.swap) block_consumer_args<T>(a.b, cola, a_packed, a_ref_stride, n_blocks, ef);
+    else block_consumer_args<T>(a.b, colb, b_packed, b_ref_stride, n_blocks, ef);
+    a.mask = reinterpret_cast<char*>(mask);
+    a.cmp_refs = rel.swap ? b_refs : a_refs;
+    a.b_refs = rel.swap ? a_refs : b_refs;
+    a.cmp_a = a.cmp_s = 0;
+    a.cmp_none = 0u;
+    a.mask_in = reinterpret_cast<const char*>(mask_in);
+    a.combine = (unsigned)combine;
+    a.bias = columns_bias(Elem<T>::BITS, is_signed != 0);
+    a.is_eq = rel.is_eq ? 1u : 0u;
+    a.invert = rel.invert ? 1u : 0u;
+    return hip_status(for_columns_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // unfor_select (fl_select.hpp).  Launched with the shape of unfor_pack_widths, as unfor_compare is.
@@ -917,6 +954,26 @@ FL_DEFINE_FOR_COMPARE_RANGE(uint8_t, u8)
 FL_DEFINE_FOR_COMPARE_RANGE(uint16_t, u16)
 FL_DEFINE_FOR_COMPARE_RANGE(uint32_t, u32)
 FL_DEFINE_FOR_COMPARE_RANGE(uint64_t, u64)
+
+#define FL_DEFINE_FOR_COMPARE_COLUMNS(T, S)                                                               \
+    int fl_##S##_unfor_compare_columns(unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, size_t brs, \
+                                       int op, int sg, int cb, const uint32_t* mi, size_t n, uint32_t* mask, void* s) \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, a, ar, b, br, mi, mask);                                                        \
+        return run_unfor_compare_columns<T>({false, wa}, a, ar, ars, {false, wb}, b, br, brs, op, sg, cb, mi, n, mask, nullptr, s); \
+    }                                                                                                     \
+    int fl_##S##_unfor_compare_columns_widths(const uint8_t* aw, const uint64_t* ao, const T* a, size_t ab, const T* ar, size_t ars, \
+                                              const uint8_t* bw, const uint64_t* bo, const T* b, size_t bb, const T* br, size_t brs, \
+                                              int op, int sg, int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, aw, ao, a, ar, bw, bo, b, br, mi, mask, ef);                                    \
+        return run_unfor_compare_columns<T>({true, 0, aw, ao, ab}, a, ar, ars, {true, 0, bw, bo, bb}, b, br, brs, op, sg, cb, mi, n, mask, ef, s); \
+    }
+
+FL_DEFINE_FOR_COMPARE_COLUMNS(uint8_t, u8)
+FL_DEFINE_FOR_COMPARE_COLUMNS(uint16_t, u16)
+FL_DEFINE_FOR_COMPARE_COLUMNS(uint32_t, u32)
+FL_DEFINE_FOR_COMPARE_COLUMNS(uint64_t, u64)
 
 FL_DEFINE_TYPE(uint8_t, u8)
 FL_DEFINE_TYPE(uint16_t, u16)

@@ -11,6 +11,7 @@
 //   15 unfor_aggregate (count / sum / min / max per block of the rows a mask keeps, from the same columns; fl_aggregate.hpp)
 //   16 unfor_compare_range (interval predicates over the same columns, chained through the mask so far; fl_for_compare_range.hpp)
 //   17 unfor_aggregate_by (count / sum / min / max per u8 key of the rows a mask keeps, value and key column both FoR-packed; fl_aggregate_by.hpp)
+//   18 unfor_compare_columns (a <op> b between two FoR-packed columns of one type, chained through the mask so far; fl_for_compare_columns.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -22,6 +23,7 @@
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
+#include "fl_for_compare_columns.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -136,7 +138,9 @@ template <> aggregate_launch_t aggregate_launcher<T>() { return &launch_block_co
 template <> for_range_launch_t for_range_launcher<T>() { return &launch_block_consumer<T, ForRangeArgs, k_unfor_compare_range<T>, false>; }
 #elif FL_FAMILY == 17
 template <> aggregate_by_launch_t aggregate_by_launcher<T>() { return &launch_aggregate_by<T>; }
+#elif FL_FAMILY == 18
+template <> for_columns_launch_t for_columns_launcher<T>() { return &launch_block_consumer<T, ForColumnsArgs, k_unfor_compare_columns<T>, false>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..17"
+#error "FL_FAMILY must be 0..6 or 8..18"
 #endif
 }  // namespace fl

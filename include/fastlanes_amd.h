@@ -569,6 +569,54 @@ FL_DECLARE_AGGREGATE_BY(uint16_t, u16)
 FL_DECLARE_AGGREGATE_BY(uint32_t, u32)
 FL_DECLARE_AGGREGATE_BY(uint64_t, u64)
 
+/*
+ * EXTENSION: a predicate BETWEEN TWO COLUMNS -- WHERE commit_date < receipt_date, WHERE bid > ask, WHERE a = b --
+ * over two FoR-packed columns of the SAME element type T and the same n_blocks, both uniform width (the first form; the two widths may
+ * differ) or both mixed width (the _widths form), chained through a mask like fl_<ty>_unfor_compare_range.  Neither column is
+ * materialised.  Defined as the composition (all arithmetic mod 2^T)
+ *     va        = unfor_pack::<WA_b>(a block b, a_references[b*a_reference_stride])[i]                               (ffor.rs:38-50)
+ *     vb        = unfor_pack::<WB_b>(b block b, b_references[b*b_reference_stride])[i]
+ *     bias      = is_signed ? 2^(T-1) : 0
+ *     hit[b][i] = ((va + bias) mod 2^T) <op> ((vb + bias) mod 2^T)             -- unsigned comparison, op an fl_cmp
+ *     FL_MASK_NEW: mask[b] = hit[b]   (mask_in ignored, may be NULL)
+ *     FL_MASK_AND: mask[b] = mask_in[b] & hit[b]          FL_MASK_OR: mask[b] = mask_in[b] | hit[b]
+ * is_signed != 0 compares the two's-complement values.  Masks have the layout of fl_<ty>_unpack_compare: 32 words per block, bit
+ * i % 32 of word b*32 + i/32.  Every valid block's 128 mask bytes are always written.  `mask` may be the same pointer as `mask_in`
+ * (in place); ANY OTHER OVERLAP of the two is the caller's error.  A reference stride of 0 broadcasts references[0].
+ * A block is answered without reading EITHER column's packed bytes when `combine` is AND and its mask_in is all zero, when `combine`
+ * is OR and its mask_in is all ones, or when the two blocks' references and widths decide it: for the ordering ops when the hulls of
+ * the two value ranges do not overlap (or touch in the one value that decides), for == / != when the two cyclic ranges are disjoint
+ * or both widths are 0.  Otherwise only the columns of width >= 1 are read: a constant block against a packed block reads one block.
+ * The mixed-width form runs the per-block device checks of fl_<ty>_unfor_pack_widths on BOTH columns: a block that fails either
+ * check is skipped, its FL_DEVERR_* bits are ORed into *err_flag, its 32 mask words are left as they were (the contract of
+ * fl_<ty>_unfor_compare_widths), and neither column is read.
+ * Either width > T is FL_ERR_WIDTH (also for an empty column); an `op` or a `combine` outside its enum FL_ERR_INDEX; n_blocks == 0
+ * FL_OK; mask_in == NULL with AND / OR, or any other required pointer NULL, FL_ERR_NULL (a column's packed pointer may be NULL only
+ * when no byte of it can be read: its width is 0, or its packed bytes are 0); the packed columns, `mask` and `mask_in` are 16-byte
+ * aligned (FL_ERR_ALIGN).
+ * Out of scope: columns of different element types, arithmetic between columns (a + b < k, SUM(a * b)), Delta columns, the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_FOR_COMPARE_COLUMNS(T, S)                                                              \
+    int fl_##S##_unfor_compare_columns(unsigned width_a, const T *a, const T *a_references, size_t a_reference_stride, \
+                                       unsigned width_b, const T *b, const T *b_references, size_t b_reference_stride, \
+                                       int op, int is_signed, int combine,                                \
+                                       const uint32_t *mask_in /* NULL with FL_MASK_NEW */,               \
+                                       size_t n_blocks, uint32_t *mask, void *stream);                    \
+    int fl_##S##_unfor_compare_columns_widths(const uint8_t *a_widths, const uint64_t *a_offsets, const T *a_packed, \
+                                              size_t a_packed_bytes, const T *a_references, size_t a_reference_stride, \
+                                              const uint8_t *b_widths, const uint64_t *b_offsets, const T *b_packed, \
+                                              size_t b_packed_bytes, const T *b_references, size_t b_reference_stride, \
+                                              int op, int is_signed, int combine,                         \
+                                              const uint32_t *mask_in /* NULL with FL_MASK_NEW */,        \
+                                              size_t n_blocks, uint32_t *mask, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_FOR_COMPARE_COLUMNS(uint8_t, u8)
+FL_DECLARE_FOR_COMPARE_COLUMNS(uint16_t, u16)
+FL_DECLARE_FOR_COMPARE_COLUMNS(uint32_t, u32)
+FL_DECLARE_FOR_COMPARE_COLUMNS(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_compare_widths = fl_##S##_unfor_compare_widths;                  \
         static constexpr auto unfor_compare_range = fl_##S##_unfor_compare_range;                    \
         static constexpr auto unfor_compare_range_widths = fl_##S##_unfor_compare_range_widths;      \
+        static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
+        static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
         static constexpr auto unfor_select_widths = fl_##S##_unfor_select_widths;                    \
         static constexpr auto unfor_aggregate = fl_##S##_unfor_aggregate;                            \
@@ -205,6 +207,13 @@ template <typename T> struct FoR : BitPacking<T> {
                                            fl_mask_combine combine, const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
                                            void* stream = nullptr)
     { detail::check(A::unfor_compare_range((unsigned)width, d_packed, d_refs, ref_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, stream), "unfor_compare_range_device"); }
+    // a <op> b between two FoR-packed columns of T with the same block count (signed: of the two's-complement values), joined with the
+    // mask so far as unfor_compare_range_device does; a block pair the references and widths decide reads neither column
+    static void unfor_compare_columns_device(std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride, std::size_t width_b,
+                                             const T* d_b, const T* d_b_refs, std::size_t b_ref_stride, fl_cmp op, bool is_signed,
+                                             fl_mask_combine combine, const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
+                                             void* stream = nullptr)
+    { detail::check(A::unfor_compare_columns((unsigned)width_a, d_a, d_a_refs, a_ref_stride, (unsigned)width_b, d_b, d_b_refs, b_ref_stride, (int)op, is_signed ? 1 : 0, (int)combine, d_mask_in, n_blocks, d_mask, stream), "unfor_compare_columns_device"); }
     // only the values of unfor_pack(..) whose mask bit is set, compacted: block b's go to d_out[d_out_offsets[b] ..] (mask_offsets_device)
     static void unfor_select_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
                                     const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
@@ -454,6 +463,16 @@ inline void unfor_compare_range_widths_device(const std::uint8_t* d_widths, cons
                                               const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
                                               std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_compare_range_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_range_widths"); }
+// ... and a predicate between two mixed-width columns of T with the same block count, a <op> b (signed: of the two's-complement values),
+// chained the same way; both columns get unfor_pack_widths' device checks, a block that fails either keeps its mask words
+template <typename T>
+inline void unfor_compare_columns_widths_device(const std::uint8_t* d_a_widths, const std::uint64_t* d_a_offsets, const T* d_a_packed,
+                                                std::size_t a_packed_bytes, const T* d_a_references, std::size_t a_reference_stride,
+                                                const std::uint8_t* d_b_widths, const std::uint64_t* d_b_offsets, const T* d_b_packed,
+                                                std::size_t b_packed_bytes, const T* d_b_references, std::size_t b_reference_stride, fl_cmp op,
+                                                bool is_signed, fl_mask_combine combine, const std::uint32_t* d_mask_in, std::size_t n_blocks,
+                                                std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_compare_columns_widths(d_a_widths, d_a_offsets, d_a_packed, a_packed_bytes, d_a_references, a_reference_stride, d_b_widths, d_b_offsets, d_b_packed, b_packed_bytes, d_b_references, b_reference_stride, (int)op, is_signed ? 1 : 0, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_columns_widths"); }
 // selection mask -> where each block's kept values start in the compacted output (elements), and how many there are in all
 inline void mask_offsets_device(const std::uint32_t* d_mask, std::size_t n_blocks, std::uint64_t* d_out_offsets, std::uint64_t* d_total = nullptr,
                                 void* stream = nullptr)

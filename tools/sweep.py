@@ -1071,6 +1071,113 @@ def main():
             del col, refs, refs_und, out, hits, masks, clustered, m10, variants
             torch.cuda.empty_cache()
         return
+    if args.cases == "compare_columns":
+        # unfor_compare_columns_widths (a < b between two mixed-width columns, chained through a mask) over the mixed-width column of --cases
+        # mixed and a second one of the same shape (its own widths, its own packed bytes).  The second column's references sit INSIDE the first
+        # one's ranges, so no block pair is decided from its metadata and whatever is saved is saved by the incoming mask.  Timed in the SAME
+        # run on the SAME buffers, round-robin: NEW; AND with an incoming mask of density 0, a clustered 1 % (one contiguous run of full
+        # blocks), a random 10 % (every block keeps something) and 100 %; an all-decided run (the second column's references pushed just past
+        # the first one's ranges); yardstick (a) two unfor_compare_widths launches, one per column, each under an undecided constant -- the
+        # same packed bytes read, two masks written; yardstick (b) the composition the call replaces, unfor_pack_widths of both columns plus
+        # the torch compare.  Every figure is the median of `reps` launches with their min .. max beside it; the device's unique id heads
+        # the table.
+        reps = max(args.reps, 5)
+        props = torch.cuda.get_device_properties(dev)
+        print(f"# device {props.name} unique id {getattr(props, 'uuid', 'unknown')}  placement {PLACEMENT}", flush=True)
+        signed_view = {"u8": torch.uint8, "u16": torch.int16, "u32": torch.int32, "u64": torch.int64}     # torch compares these
+
+        def round_robin(variants):
+            """{name: [ms, ...]}: `reps` timed launches of every variant, interleaved, after two untimed rounds"""
+            for _ in range(2):
+                for f in variants.values():
+                    f()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in variants}
+            for _ in range(reps):
+                for k, f in variants.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); f(); b.record(); b.synchronize()
+                    ms[k].append(a.elapsed_time(b))
+            return ms
+
+        def random_words(n, density, seed):
+            """int32 words of a random mask, built 32 Ki blocks at a time"""
+            g = torch.Generator(device=dev); g.manual_seed(seed)
+            out = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            sh = torch.arange(32, device=dev)
+            for b0 in range(0, n, 32768):
+                nb = min(32768, n - b0)
+                bits = torch.rand(nb * 1024, device=dev, generator=g) < density
+                w64 = (bits.view(-1, 32).to(torch.int64) << sh).sum(dim=1)
+                out[b0 * 32:(b0 + nb) * 32] = torch.where(w64 >= 1 << 31, w64 - (1 << 32), w64).to(torch.int32)
+            return out
+
+        def show(ms):
+            v = sorted(ms)
+            return f"{v[len(v) // 2]:9.4f} ms ({v[0]:.4f} .. {v[-1]:.4f})"
+
+        for ty in ("u32", "u64", "u16", "u8"):
+            if args.types and ty not in args.types.split(","):
+                continue
+            T, esz = ESZ[ty] * 8, ESZ[ty]
+            n = max(64, int(args.gb * 1e9 / (128 * T * 1.5)) // 2)          # two columns share the --gb budget
+            as_refs = lambda v: v.view(torch.uint8).view(-1, 8)[:, :esz].contiguous().view(TDT[ty]).reshape(-1)   # int64 -> T, mod 2^T
+            cols = []
+            for c in (0, 1):
+                g = torch.Generator(device=dev); g.manual_seed(31 + T + 1000 * c)
+                w = torch.randint(1, T, (n,), dtype=torch.int64, device=dev, generator=g).to(torch.uint8)
+                off, total = fl.widths_to_offsets(ty, w)
+                cols.append((w, off, rnd(int(total.item()), 1 + 10 * c).view(TDT[ty])))
+            (wa, oa, ca), (wb, ob, cb) = cols
+            pbytes = ca.numel() * esz + cb.numel() * esz
+            # a: references k - 1 - (x mod (2^WA - 1)): every block's range holds k - 1 and k (the undecided constant of yardstick (a));
+            # b for yardstick (a): the same construction on its own widths
+            k = 1 << (T - 1)
+            span_a = (torch.ones(n, dtype=torch.int64, device=dev) << wa.to(torch.int64)) - 1
+            span_b = (torch.ones(n, dtype=torch.int64, device=dev) << wb.to(torch.int64)) - 1
+            x = rnd(n * 8, 5).view(torch.int64) & ((1 << 62) - 1)
+            y = rnd(n * 8, 6).view(torch.int64) & ((1 << 62) - 1)
+            ra64 = (k - 1) - x % span_a
+            ra, rb_own = as_refs(ra64), as_refs((k - 1) - y % span_b)
+            rb_in = as_refs(ra64 + y % (span_a + 1))                        # b starts inside a's range: the ranges overlap, nothing is decided
+            ra_dec = torch.zeros(n, dtype=TDT[ty], device=dev)              # a in [0, 2^WA - 1], b from 2^WA on (no wrap: W <= T - 1): a < b everywhere
+            rb_dec = as_refs(span_a + 1)
+            out = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            out2 = torch.empty(n * 32, dtype=torch.int32, device=dev)
+            clustered = torch.zeros(n * 32, dtype=torch.int32, device=dev)
+            run = max(1, n // 100)
+            clustered[(n // 3) * 32:(n // 3 + run) * 32] = -1
+            masks = {"AND density 0": torch.zeros(n * 32, dtype=torch.int32, device=dev), "AND clustered 1 %": clustered,
+                     "AND random 10 %": random_words(n, 0.10, 77 + T), "AND density 100 %": torch.full((n * 32,), -1, dtype=torch.int32, device=dev)}
+            una, unb = torch.empty(n * 1024, dtype=TDT[ty], device=dev), torch.empty(n * 1024, dtype=TDT[ty], device=dev)
+            hit = torch.empty(n * 1024, dtype=torch.bool, device=dev)
+            print(f"# {ty}: n = {n} blocks per column, packed {pbytes / 1e9:.2f} GB in both ({pbytes / n:.1f} B/block pair), {reps} launches each, round-robin", flush=True)
+
+            def columns(ra_, rb_, **kw):
+                return fl.unfor_compare_columns_widths(wa, oa, ca, ra_, "<", wb, ob, cb, rb_, output=out, check=False, **kw)
+
+            def two_compares():
+                fl.unfor_compare_widths(wa, oa, ca, ra, "<", k, output=out, check=False)
+                fl.unfor_compare_widths(wb, ob, cb, rb_own, "<", k, output=out2, check=False)
+
+            def composition():
+                fl.unfor_pack_widths(wa, oa, ca, ra, output=una, check=False)
+                fl.unfor_pack_widths(wb, ob, cb, rb_in, output=unb, check=False)
+                torch.lt(una.view(signed_view[ty]), unb.view(signed_view[ty]), out=hit)
+
+            variants = {"2 x unfor_compare_widths undecided": two_compares, "NEW undecided": lambda: columns(ra, rb_in),
+                        "NEW all decided": lambda: columns(ra_dec, rb_dec)}
+            for name, m in masks.items():
+                variants[name] = lambda m=m: columns(ra, rb_in, mask=m, combine="and")
+            variants["2 x unfor_pack_widths + torch.lt"] = composition
+            ms = round_robin(variants)
+            med = {kk: sorted(v)[len(v) // 2] for kk, v in ms.items()}
+            for kk in variants:
+                print(f"{kk:36s} {ty:4s} {show(ms[kk])}  {n / med[kk] / 1e6:8.3f} Gblock pairs/s  x{med[kk] / med['2 x unfor_compare_widths undecided']:.3f} of "
+                      f"2 x compare, x{med[kk] / med['NEW undecided']:.3f} of NEW undecided, x{med[kk] / med['NEW all decided']:.3f} of all decided", flush=True)
+            del cols, ca, cb, una, unb, hit, out, out2, masks, clustered, variants
+            torch.cuda.empty_cache()
+        return
     if args.cases == "single":
         # batched unpack_single (bitpacking.rs:132-200; benches/bitpacking.rs:36-65 times one lookup): k lookups into an n-block column
         # -- random, sorted, strided (one per block: every lookup a different block) and dense (all 1024 of consecutive blocks);
