@@ -127,6 +127,10 @@ _SIGNATURES = (
     # ({vty} as above: these rows' refusals are pinned by tests/test_for_compare_columns_cpu.py)
     ("FOR_COMPARE_COLUMNS", "fl_{vty}_unfor_compare_columns", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _P]),
     ("FOR_COMPARE_COLUMNS", "fl_{vty}_unfor_compare_columns_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _I, _I, _I, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_AGGREGATE_COLUMNS (device tier): count / sum / min / max per block of a * b, a + b or a - b between two FoR-packed columns
+    # of one element type under a mask ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_columns_cpu.py)
+    ("AGGREGATE_COLUMNS", "fl_{vty}_unfor_aggregate_columns", _I, [_I, _U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
+    ("AGGREGATE_COLUMNS", "fl_{vty}_unfor_aggregate_columns_widths", _I, [_I, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -186,6 +190,11 @@ def aggregate_by_symbols():
 def for_compare_columns_symbols():
     """The symbols FL_DECLARE_FOR_COMPARE_COLUMNS declares: for all four element types the two column-against-column entry points."""
     return _symbols("FOR_COMPARE_COLUMNS")
+
+
+def aggregate_columns_symbols():
+    """The symbols FL_DECLARE_AGGREGATE_COLUMNS declares: for all four element types the two aggregate-of-two-columns entry points."""
+    return _symbols("AGGREGATE_COLUMNS")
 
 
 _LIB = None

@@ -553,6 +553,40 @@ class FoR:
         return _aggregate_by_call(f"fl_{ty}_unfor_aggregate_by", src, n, (width, src.ptr, aux.ptr, stride, key_width, ksrc.ptr, kaux.ptr, kstride),
                                   mask, result, check)
 
+    EXPR = {"*": 0, "+": 1, "-": 2}         # include/fastlanes_amd.h: fl_expr
+
+    @staticmethod
+    def unfor_aggregate_columns(width_a, a, a_reference, expr, width_b, b, b_reference, mask=None, n_blocks=None, block_aggs=None,
+                                check=True):
+        """COUNT / SUM / MIN / MAX of an expression between two columns: with va = FoR.unfor_pack(width_a, a, a_reference)[i] and vb
+        the same of column `b` (the same element type and block count; the widths may differ), x = va `expr` vb, expr one of '*',
+        '+', '-' (a - b), over the rows where `mask` (the layout unfor_compare returns: a CUDA int32 tensor of 32 words per block;
+        None: every row, and no mask is read) has a 1 -- SELECT SUM(price * discount) WHERE <mask>, without materialising either
+        column.  Both values are zero-extended to 64 bits BEFORE the operation: u8 / u16 / u32 products and sums are exact, u64
+        wraps; a difference below zero is its two's-complement bit pattern, so the sum is right as int64 and min / max compare the
+        patterns as unsigned numbers.  Returns (result, block_aggs) as FoR.unfor_aggregate does: a CUDA int64[4] tensor and a CUDA
+        int64[n_blocks, 4] tensor (`block_aggs` if given) of count, sum (wrapping mod 2^64), min, max as uint64 bit patterns;
+        nothing kept gives (0, 0, 2^64 - 1, 0).  A block whose mask is empty, or whose two widths are both 0, reads neither column;
+        a column of width 0 is never read.  Device tier only; no host round trip.  n_blocks is only needed when both widths are 0
+        and there is no mask."""
+        ex = _expr_code(expr)
+        sa, sb = _Arg(a), _Arg(b)
+        ty = sa.ty
+        if sb.ty != ty:
+            raise TypeError(f"both columns must have one element type, got {ty} and {sb.ty}")
+        _check_width(ty, width_b, "unfor_aggregate_columns")
+        n = _uniform_blocks(sa, width_a, "unfor_aggregate_columns", n_blocks, (b if width_b else None, packed_len(ty, width_b)),
+                            (mask if _is_torch(mask) else None, 32))
+        if _uniform_blocks(sb, width_b, "unfor_aggregate_columns", n) != n:
+            raise ValueError(f"column b does not hold column a's {n} blocks")
+        if not sa.torch:
+            raise TypeError("unfor_aggregate_columns is device tier (pass CUDA tensors)")
+        _same_tier(sa, sb)
+        ra, stride_a, _ = FoR._ref(sa, ty, a_reference, n)
+        rb, stride_b, _ = FoR._ref(sb, ty, b_reference, n)
+        return _aggregate_call(f"fl_{ty}_unfor_aggregate_columns", sa, n,
+                               (ex, width_a, sa.ptr, ra.ptr, stride_a, width_b, sb.ptr, rb.ptr, stride_b), mask, block_aggs, check)
+
 
 class Delta:
     """delta.rs:6-17.  `base` holds LANES = 1024/T elements per block."""
@@ -977,6 +1011,33 @@ def unfor_aggregate_widths(widths, offsets, packed, references, mask=None, block
     src = _Arg(packed)
     n, lead = _widths_column("unfor_aggregate_widths", src, widths, offsets, references=references)
     return _aggregate_call(f"fl_{src.ty}_unfor_aggregate_widths", src, n, lead, mask, block_aggs, check)
+
+
+def _expr_code(expr):
+    """'*', '+', '-' -> fl_expr; anything else is refused here, before a buffer is looked at"""
+    if not isinstance(expr, str) or expr not in FoR.EXPR:
+        raise ValueError(f"expr must be one of {', '.join(map(repr, FoR.EXPR))}, got {expr!r}")
+    return FoR.EXPR[expr]
+
+
+def unfor_aggregate_columns_widths(a_widths, a_offsets, a_packed, a_references, expr, b_widths, b_offsets, b_packed, b_references,
+                                   mask=None, block_aggs=None, check=True):
+    """FoR.unfor_aggregate_columns over two mixed-width columns of the same element type and block count: COUNT / SUM / MIN / MAX of
+    va `expr` vb ('*', '+', '-'; both values zero-extended to 64 bits first) of the values unfor_pack_widths yields for column a and
+    for column b in the same rows, where `mask` (32 words per block, unfor_compare_widths' layout; None: everywhere) has a 1.
+    Returns (result, block_aggs) as FoR.unfor_aggregate does.  The per-block device checks of unfor_pack_widths run on BOTH columns:
+    a block that fails either is skipped (neither column is read) and ITS SLOT HOLDS THE IDENTITY (0, 0, 2^64 - 1, 0), so `result`
+    combines the valid blocks; `check=True` reads the device error flag back (one sync) and raises, `check=False` stays
+    asynchronous."""
+    ex = _expr_code(expr)
+    sa, sb = _Arg(a_packed), _Arg(b_packed)
+    if sb.ty != sa.ty:
+        raise TypeError(f"both columns must have one element type, got {sa.ty} and {sb.ty}")
+    if _numel(b_widths) != _numel(a_widths):
+        raise ValueError(f"column b holds {_numel(b_widths)} blocks, column a {_numel(a_widths)}")
+    n, lead_a = _widths_column("unfor_aggregate_columns_widths", sa, a_widths, a_offsets, sb, references=a_references)
+    _, lead_b = _widths_column("unfor_aggregate_columns_widths", sb, b_widths, b_offsets, sa, references=b_references)
+    return _aggregate_call(f"fl_{sa.ty}_unfor_aggregate_columns_widths", sa, n, (ex, *lead_a, *lead_b), mask, block_aggs, check)
 
 
 AGGREGATE_BY_GROUPS = 256                   # include/fastlanes_amd.h: one slot per possible u8 key

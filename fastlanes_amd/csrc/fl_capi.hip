@@ -22,6 +22,7 @@
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
 #include "fl_for_compare_columns.hpp"
+#include "fl_aggregate_columns.hpp"
 #include "fl_host_tier.hpp"
 
 #include <algorithm>
@@ -528,6 +529,31 @@ int run_unfor_aggregate(const Column& col, const T* packed, const T* refs, size_
     return hip_status(aggregate_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
+// unfor_aggregate_columns (fl_aggregate_columns.hpp): two columns of T of the same form, both uniform or both mixed, met element by
+// element under `expr` and aggregated per block as run_unfor_aggregate does (a block that fails either column's checks leaves the
+// identity in its slot).  The same launch shape; the checks in the order of run_unfor_aggregate, `expr` where a `combine` is judged.
+template <typename T>
+int run_unfor_aggregate_columns(int expr, const Column& cola, const T* a_packed, const T* a_refs, size_t a_ref_stride, const Column& colb,
+                                const T* b_packed, const T* b_refs, size_t b_ref_stride, const uint32_t* mask, size_t n_blocks,
+                                void* block_aggs, uint32_t* err_flag, void* stream)
+{
+    if ((!cola.mixed && over_width<T>(cola.width)) || (!colb.mixed && over_width<T>(colb.width))) return FL_ERR_WIDTH;
+    if (!expr_valid(expr)) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (!block_consumer_column(cola, a_packed, a_refs) || !block_consumer_column(colb, b_packed, b_refs) || !block_aggs) return FL_ERR_NULL;
+    if (misaligned(a_packed) || misaligned(b_packed) || misaligned(mask) || misaligned(block_aggs)) return FL_ERR_ALIGN;
+    AggregateColumnsArgs a;
+    uint32_t* ef = cola.mixed ? err_flag : nullptr;
+    const WaveShape sh = block_consumer_args<T>(a, cola, a_packed, a_ref_stride, n_blocks, ef);
+    block_consumer_args<T>(a.b, colb, b_packed, b_ref_stride, n_blocks, ef);
+    a.mask = mask;
+    a.aggs = static_cast<char*>(block_aggs);
+    a.agg_refs = a_refs;
+    a.b_refs = b_refs;
+    a.expr = (unsigned)expr;
+    return hip_status(aggregate_columns_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
 // unfor_aggregate_by (fl_aggregate_by.hpp): a value column of T and a u8 key column of the same form, both uniform or both mixed; a
 // block that fails either column's checks contributes nothing.  `result` (256 slots) is written by EVERY call -- the init launch also
 // answers an empty column -- so it is required and checked before the empty-column return.  The persistent grid takes the policy's
@@ -974,6 +1000,26 @@ FL_DEFINE_FOR_COMPARE_COLUMNS(uint8_t, u8)
 FL_DEFINE_FOR_COMPARE_COLUMNS(uint16_t, u16)
 FL_DEFINE_FOR_COMPARE_COLUMNS(uint32_t, u32)
 FL_DEFINE_FOR_COMPARE_COLUMNS(uint64_t, u64)
+
+#define FL_DEFINE_AGGREGATE_COLUMNS(T, S)                                                                 \
+    int fl_##S##_unfor_aggregate_columns(int ex, unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, \
+                                         size_t brs, const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, void* s) \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, a, ar, b, br, mask, aggs, ef);                                                  \
+        return run_unfor_aggregate_columns<T>(ex, {false, wa}, a, ar, ars, {false, wb}, b, br, brs, mask, n, aggs, ef, s); \
+    }                                                                                                     \
+    int fl_##S##_unfor_aggregate_columns_widths(int ex, const uint8_t* aw, const uint64_t* ao, const T* a, size_t ab, const T* ar, size_t ars, \
+                                                const uint8_t* bw, const uint64_t* bo, const T* b, size_t bb, const T* br, size_t brs, \
+                                                const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, void* s) \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, aw, ao, a, ar, bw, bo, b, br, mask, aggs, ef);                                  \
+        return run_unfor_aggregate_columns<T>(ex, {true, 0, aw, ao, ab}, a, ar, ars, {true, 0, bw, bo, bb}, b, br, brs, mask, n, aggs, ef, s); \
+    }
+
+FL_DEFINE_AGGREGATE_COLUMNS(uint8_t, u8)
+FL_DEFINE_AGGREGATE_COLUMNS(uint16_t, u16)
+FL_DEFINE_AGGREGATE_COLUMNS(uint32_t, u32)
+FL_DEFINE_AGGREGATE_COLUMNS(uint64_t, u64)
 
 FL_DEFINE_TYPE(uint8_t, u8)
 FL_DEFINE_TYPE(uint16_t, u16)

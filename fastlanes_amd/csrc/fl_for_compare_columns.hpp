@@ -25,7 +25,7 @@
 // Every valid block's 128 bytes are always written.  `mask` may be `mask_in` itself: a wavefront reads a block's incoming mask before
 // it stores that block, and no other wavefront touches those bytes.  Every launch shape for_each_block_of_wave hands out is served
 // block by block through the wavefront's first image; a several-blocks-in-flight form for the narrow types is an open end.
-// Out of scope: columns of different element types, arithmetic between columns, Delta columns, the host tier.
+// Out of scope: columns of different element types, arithmetic inside the predicate (fl_aggregate_columns.hpp aggregates a o b), Delta columns, the host tier.
 // LDS is wave-local (in-order per wave): no s_barrier.  Every store is a vector store.
 #pragma once
 #include "fl_for_compare_range.hpp"

@@ -12,6 +12,7 @@
 //   16 unfor_compare_range (interval predicates over the same columns, chained through the mask so far; fl_for_compare_range.hpp)
 //   17 unfor_aggregate_by (count / sum / min / max per u8 key of the rows a mask keeps, value and key column both FoR-packed; fl_aggregate_by.hpp)
 //   18 unfor_compare_columns (a <op> b between two FoR-packed columns of one type, chained through the mask so far; fl_for_compare_columns.hpp)
+//   19 unfor_aggregate_columns (count / sum / min / max per block of a * b, a + b or a - b between two such columns under a mask; fl_aggregate_columns.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -24,6 +25,7 @@
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
 #include "fl_for_compare_columns.hpp"
+#include "fl_aggregate_columns.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -140,7 +142,9 @@ template <> for_range_launch_t for_range_launcher<T>() { return &launch_block_co
 template <> aggregate_by_launch_t aggregate_by_launcher<T>() { return &launch_aggregate_by<T>; }
 #elif FL_FAMILY == 18
 template <> for_columns_launch_t for_columns_launcher<T>() { return &launch_block_consumer<T, ForColumnsArgs, k_unfor_compare_columns<T>, false>; }
+#elif FL_FAMILY == 19
+template <> aggregate_columns_launch_t aggregate_columns_launcher<T>() { return &launch_block_consumer<T, AggregateColumnsArgs, k_unfor_aggregate_columns<T>, false>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..18"
+#error "FL_FAMILY must be 0..6 or 8..19"
 #endif
 }  // namespace fl

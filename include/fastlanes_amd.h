@@ -594,7 +594,8 @@ FL_DECLARE_AGGREGATE_BY(uint64_t, u64)
  * FL_OK; mask_in == NULL with AND / OR, or any other required pointer NULL, FL_ERR_NULL (a column's packed pointer may be NULL only
  * when no byte of it can be read: its width is 0, or its packed bytes are 0); the packed columns, `mask` and `mask_in` are 16-byte
  * aligned (FL_ERR_ALIGN).
- * Out of scope: columns of different element types, arithmetic between columns (a + b < k, SUM(a * b)), Delta columns, the host tier.
+ * Out of scope: columns of different element types, arithmetic inside the predicate (a + b < k; an aggregate of a * b, a + b or a - b is
+ * fl_<ty>_unfor_aggregate_columns), Delta columns, the host tier.
  * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
  * are pinned surfaces.)
  */
@@ -616,6 +617,54 @@ FL_DECLARE_FOR_COMPARE_COLUMNS(uint8_t, u8)
 FL_DECLARE_FOR_COMPARE_COLUMNS(uint16_t, u16)
 FL_DECLARE_FOR_COMPARE_COLUMNS(uint32_t, u32)
 FL_DECLARE_FOR_COMPARE_COLUMNS(uint64_t, u64)
+
+/*
+ * EXTENSION: an aggregate of ARITHMETIC BETWEEN TWO COLUMNS -- SELECT SUM(price * discount), SUM(bid - ask),
+ * MAX(a + b), a dot product -- over two FoR-packed columns of the SAME element type T and the same n_blocks, both uniform width (the
+ * first form; the two widths may differ) or both mixed width (the _widths form), over the rows a selection mask keeps.  Neither
+ * column is materialised.  Defined as the composition
+ *     va      = unfor_pack::<WA_b>(a block b, a_references[b*a_reference_stride])[i]                                 (ffor.rs:38-50)
+ *     vb      = unfor_pack::<WB_b>(b block b, b_references[b*b_reference_stride])[i]
+ *     x[b][i] = (zext64(va) o zext64(vb)) mod 2^64          o = `expr`, an fl_expr: FL_EXPR_MUL a * b, FL_EXPR_ADD a + b, FL_EXPR_SUB a - b
+ *     agg_b   = { count, sum of x (wrapping mod 2^64), min x, max x } over the i whose bit is set in block b of `mask`
+ * with fl_block_aggregate, its identity {0, 0, UINT64_MAX, 0} for a block that keeps nothing, `combine` and the mask layout exactly
+ * those of fl_<ty>_unfor_aggregate; mask == NULL keeps every row, and no mask is read.  The values are widened to 64 bits BEFORE the
+ * operation: u8 / u16 / u32 products and sums are exact, u64 ones wrap.  A difference below zero is its two's-complement bit pattern,
+ * so the SUM is right mod 2^64 (read it as int64_t); MIN AND MAX COMPARE THE PATTERNS AS UNSIGNED NUMBERS: every negative difference
+ * lies above every non-negative one.  A reference stride of 0 broadcasts references[0]; one zero reference with stride 0 on both
+ * sides gives the plain bit-packed product.
+ * block_aggs[b] = agg_b for EVERY block (n_blocks fl_block_aggregate); the total is fl_aggregate_reduce over those slots, as for
+ * fl_<ty>_unfor_aggregate.  A block whose mask is empty, or whose two widths are both 0 (every row holds ra o rb), is answered from
+ * its metadata: neither column's packed bytes are read.  A column whose width is 0 in a block is never read there: a constant block
+ * against a packed block reads one block.  The mixed-width form runs the per-block device checks of fl_<ty>_unfor_pack_widths on BOTH
+ * columns: a block that fails either check raises its FL_DEVERR_* bits in *err_flag, reads neither column and ITS SLOT RECEIVES THE
+ * IDENTITY (the contract of fl_<ty>_unfor_aggregate_widths: the slot feeds a reduction).
+ * Either width > T is FL_ERR_WIDTH (also for an empty column); an `expr` outside fl_expr FL_ERR_INDEX; n_blocks == 0 FL_OK; a
+ * required pointer NULL FL_ERR_NULL (a column's packed pointer may be NULL only when no byte of it can be read: its width is 0, or
+ * its packed bytes are 0; `mask` may be NULL); the packed columns, `mask` and `block_aggs` are 16-byte aligned (FL_ERR_ALIGN).
+ * Out of scope: signed (sign-extending) columns, columns of different element types, Delta columns, grouping, the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+typedef enum fl_expr { FL_EXPR_MUL = 0, FL_EXPR_ADD = 1, FL_EXPR_SUB = 2 } fl_expr;
+
+#define FL_DECLARE_AGGREGATE_COLUMNS(T, S)                                                                \
+    int fl_##S##_unfor_aggregate_columns(int expr, unsigned width_a, const T *a, const T *a_references,   \
+                                         size_t a_reference_stride, unsigned width_b, const T *b,         \
+                                         const T *b_references, size_t b_reference_stride,                \
+                                         const uint32_t *mask /* may be NULL */, size_t n_blocks,         \
+                                         void *block_aggs, uint32_t *err_flag, void *stream);             \
+    int fl_##S##_unfor_aggregate_columns_widths(int expr, const uint8_t *a_widths, const uint64_t *a_offsets, const T *a_packed, \
+                                                size_t a_packed_bytes, const T *a_references, size_t a_reference_stride, \
+                                                const uint8_t *b_widths, const uint64_t *b_offsets, const T *b_packed, \
+                                                size_t b_packed_bytes, const T *b_references, size_t b_reference_stride, \
+                                                const uint32_t *mask /* may be NULL */, size_t n_blocks,  \
+                                                void *block_aggs, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_AGGREGATE_COLUMNS(uint8_t, u8)
+FL_DECLARE_AGGREGATE_COLUMNS(uint16_t, u16)
+FL_DECLARE_AGGREGATE_COLUMNS(uint32_t, u32)
+FL_DECLARE_AGGREGATE_COLUMNS(uint64_t, u64)
 
 #ifdef __cplusplus
 }

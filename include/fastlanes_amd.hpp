@@ -71,6 +71,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_aggregate_widths = fl_##S##_unfor_aggregate_widths;              \
         static constexpr auto unfor_aggregate_by = fl_##S##_unfor_aggregate_by;                      \
         static constexpr auto unfor_aggregate_by_widths = fl_##S##_unfor_aggregate_by_widths;        \
+        static constexpr auto unfor_aggregate_columns = fl_##S##_unfor_aggregate_columns;            \
+        static constexpr auto unfor_aggregate_columns_widths = fl_##S##_unfor_aggregate_columns_widths; \
         static constexpr auto unpack_mixed = fl_##S##_unpack_mixed;                                  \
         static constexpr auto pack_mixed = fl_##S##_pack_mixed;                                      \
         static constexpr auto unpack_widths = fl_##S##_unpack_widths;                                \
@@ -232,6 +234,14 @@ template <typename T> struct FoR : BitPacking<T> {
                                           const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_result,
                                           std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
     { detail::check(A::unfor_aggregate_by((unsigned)width, d_packed, d_refs, ref_stride, (unsigned)key_width, d_keys, d_key_refs, key_ref_stride, d_mask, n_blocks, d_result, d_err_flag, stream), "unfor_aggregate_by_device"); }
+    // count / sum / min / max per block of a * b, a + b or a - b between two FoR-packed columns of T with the same block count, the values
+    // zero-extended to 64 bits first (a negative difference is its two's-complement pattern; min / max compare the patterns unsigned), over
+    // the rows whose mask bit is set (d_mask == nullptr: every row); neither column is materialised; aggregate_reduce_device combines the slots
+    static void unfor_aggregate_columns_device(fl_expr expr, std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride,
+                                               std::size_t width_b, const T* d_b, const T* d_b_refs, std::size_t b_ref_stride,
+                                               const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_block_aggs,
+                                               std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_aggregate_columns((int)expr, (unsigned)width_a, d_a, d_a_refs, a_ref_stride, (unsigned)width_b, d_b, d_b_refs, b_ref_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_columns_device"); }
 };
 
 // delta.rs:6-17
@@ -500,6 +510,16 @@ inline void unfor_aggregate_by_widths_device(const std::uint8_t* d_widths, const
                                              const std::uint8_t* d_key_references, std::size_t key_reference_stride, const std::uint32_t* d_mask,
                                              std::size_t n_blocks, fl_block_aggregate* d_result, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_aggregate_by_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_key_widths, d_key_offsets, d_keys, keys_bytes, d_key_references, key_reference_stride, d_mask, n_blocks, d_result, d_err_flag, stream), "unfor_aggregate_by_widths"); }
+// unfor_aggregate_columns over two mixed-width columns of T with the same block count: count / sum / min / max per block of a * b, a + b or
+// a - b; both columns get unfor_pack_widths' device checks, a block that fails either gets the identity
+template <typename T>
+inline void unfor_aggregate_columns_widths_device(fl_expr expr, const std::uint8_t* d_a_widths, const std::uint64_t* d_a_offsets, const T* d_a_packed,
+                                                  std::size_t a_packed_bytes, const T* d_a_references, std::size_t a_reference_stride,
+                                                  const std::uint8_t* d_b_widths, const std::uint64_t* d_b_offsets, const T* d_b_packed,
+                                                  std::size_t b_packed_bytes, const T* d_b_references, std::size_t b_reference_stride,
+                                                  const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_block_aggs,
+                                                  std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_aggregate_columns_widths((int)expr, d_a_widths, d_a_offsets, d_a_packed, a_packed_bytes, d_a_references, a_reference_stride, d_b_widths, d_b_offsets, d_b_packed, b_packed_bytes, d_b_references, b_reference_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_columns_widths"); }
 // per-block aggregates -> the column's: counts and sums added (wrapping), the smallest min, the largest max; no blocks: the identity
 inline void aggregate_reduce_device(const fl_block_aggregate* d_block_aggs, std::size_t n_blocks, fl_block_aggregate* d_result, void* stream = nullptr)
 { detail::check(fl_aggregate_reduce(d_block_aggs, n_blocks, d_result, stream), "aggregate_reduce"); }
