@@ -131,6 +131,10 @@ _SIGNATURES = (
     # of one element type under a mask ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_columns_cpu.py)
     ("AGGREGATE_COLUMNS", "fl_{vty}_unfor_aggregate_columns", _I, [_I, _U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_COLUMNS", "fl_{vty}_unfor_aggregate_columns_widths", _I, [_I, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_FOR_COMPARE_IN (device tier): set membership (a window of the value domain plus a bitmap) chained through a mask
+    # ({vty} as above: these rows' refusals are pinned by tests/test_for_compare_in_cpu.py)
+    ("FOR_COMPARE_IN", "fl_{vty}_unfor_compare_in", _I, [_U, _P, _P, _Z, _T, _Q, _P, _I, _I, _P, _Z, _P, _P]),
+    ("FOR_COMPARE_IN", "fl_{vty}_unfor_compare_in_widths", _I, [_P, _P, _P, _Z, _P, _Z, _T, _Q, _P, _I, _I, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -195,6 +199,11 @@ def for_compare_columns_symbols():
 def aggregate_columns_symbols():
     """The symbols FL_DECLARE_AGGREGATE_COLUMNS declares: for all four element types the two aggregate-of-two-columns entry points."""
     return _symbols("AGGREGATE_COLUMNS")
+
+
+def for_compare_in_symbols():
+    """The symbols FL_DECLARE_FOR_COMPARE_IN declares: for all four element types the two set-membership entry points."""
+    return _symbols("FOR_COMPARE_IN")
 
 
 _LIB = None

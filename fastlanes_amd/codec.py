@@ -462,6 +462,33 @@ class FoR:
         return out
 
     @staticmethod
+    def unfor_compare_in(width, packed, reference, members, negate=False, mask=None, combine="new", n_blocks=None, output=None):
+        """Set membership chained through a mask (WHERE x IN (...)): with v = FoR.unfor_pack(width, block b, reference)[i],
+        hit = (v is a member of `members`) != negate.  `members` is a member_set result for the column's element type, or anything
+        member_set accepts (it is then built here, on every call: build it once for a set that is used again).  combine "new": the
+        result is hit (`mask` is ignored); "and" / "or": `mask` & hit / `mask` | hit, `mask` a CUDA int32 tensor of 32 words per block
+        (the layout unfor_compare returns).  A block whose values all lie outside the set's window, a width-0 block, a block whose
+        `mask` is all zero under "and", and one whose `mask` is all ones under "or" are answered without reading their packed bytes.
+        `output` may be `mask` itself (in place).  Device tier only; returns a CUDA int32 tensor of 32 words per block (`output` if
+        given).  n_blocks is only needed for width == 0 without a mask or an output."""
+        import torch
+        cb = _range_combine(combine, mask)
+        if cb and _is_torch(mask) and _is_torch(packed) and 0 < width <= _lib.BITS[_ty_of(packed)] and \
+                mask.numel() * packed_len(_ty_of(packed), width) != 32 * packed.numel():
+            raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block of {packed_len(_ty_of(packed), width)} packed elements")
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_compare_in is device tier (pass CUDA tensors)")
+        n = _uniform_blocks(src, width, "unfor_compare_in", n_blocks, (mask if cb and _is_torch(mask) else None, 32), (output, 32))
+        m = _select_mask(src, mask, n) if cb else None
+        out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_in")
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        _launch(f"fl_{ty}_unfor_compare_in", src.x.device, width, src.ptr, aux.ptr, stride, *_member_args(ty, members, src.x.device),
+                int(bool(negate)), cb, m.ptr if m is not None and n else None, n, out.data_ptr())
+        return out
+
+    @staticmethod
     def unfor_compare_columns(width_a, a, a_reference, op, width_b, b, b_reference, *, signed=False, mask=None, combine="new", n_blocks=None,
                               output=None):
         """A predicate between two columns, chained through a mask: with va = FoR.unfor_pack(width_a, a block, a_reference)[i] and vb
@@ -883,6 +910,129 @@ def unfor_compare_range_widths(widths, offsets, packed, references, lo, hi, mask
     _launch(f"fl_{ty}_unfor_compare_range_widths", src.x.device, *lead, _scalar(ty, lo), _scalar(ty, hi), cb,
             m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_unfor_compare_range_widths")    # bitpacking.rs:93,126 unreachable!(); :111-113
+    return out
+
+
+class MemberSet:
+    """A member set for unfor_compare_in (member_set builds it): the element type `ty`, and a window of the value domain plus a
+    bitmap -- bit j of `words` (bit j % 32 of word j // 32), 0 <= j < `bits`, says whether the bit pattern (`lo` + j) mod 2^T is a
+    member.  `words` is a numpy uint32 array, or a CUDA int32 tensor when the set was built for a device; on(device) is the bitmap on
+    that device (uploaded once per device and kept)."""
+    __slots__ = ("ty", "lo", "bits", "words", "_on")
+
+    def __init__(self, ty, lo, bits, words):
+        self.ty, self.lo, self.bits, self.words, self._on = ty, lo, bits, words, {}
+
+    def __iter__(self):
+        return iter((self.ty, self.lo, self.bits, self.words))
+
+    def __repr__(self):
+        return f"MemberSet({self.ty}, lo={self.lo}, bits={self.bits})"
+
+    def on(self, device):
+        import torch
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if _is_torch(self.words):
+            if self.words.device != device:
+                raise ValueError(f"tensors live on different devices ({device} vs {self.words.device})")
+            return self.words
+        if device not in self._on:
+            self._on[device] = torch.from_numpy(self.words.view(np.int32)).to(device)
+        return self._on[device]
+
+
+def _member_patterns(ty, members, signed):
+    """The distinct bit patterns of `members`, ascending, as numpy uint64."""
+    T = _lib.BITS[ty]
+    M = (1 << T) - 1
+    if _is_torch(members):
+        if members.dtype.is_floating_point:
+            raise TypeError(f"members must be integers, got {members.dtype}")
+        members = members.detach().cpu().contiguous().numpy()
+    if isinstance(members, np.ndarray):
+        if members.dtype.kind not in "ui":
+            raise TypeError(f"members must be integers, got dtype {members.dtype}")
+        a = members.reshape(-1)
+        lo, hi = (-(1 << (T - 1)), (1 << (T - 1)) - 1) if signed else (0, M)
+        if a.size and (int(a.min()) < lo or int(a.max()) > hi):
+            raise ValueError(f"members must lie in [{lo}, {hi}] ({'i' if signed else 'u'}{T})")
+        if a.dtype.kind == "i":
+            a = a.astype(np.int64).view(np.uint64)                         # two's complement, sign-extended to 64 bits
+        return np.unique(a.astype(np.uint64) & np.uint64(M))
+    vals = [int(v) for v in members]
+    lo, hi = (-(1 << (T - 1)), (1 << (T - 1)) - 1) if signed else (0, M)
+    if any(v < lo or v > hi for v in vals):
+        raise ValueError(f"members must lie in [{lo}, {hi}] ({'i' if signed else 'u'}{T})")
+    return np.unique(np.array([v & M for v in vals], dtype=np.uint64))
+
+
+def member_set(ty, members, signed=False, max_bits=1 << 27, device=None):
+    """The member set of `members` for unfor_compare_in over a column of element type `ty` ("u8" .. "u64"): a MemberSet (ty, lo,
+    bits, words).  `members`: an iterable, a numpy array or a torch tensor of integers -- values of the element type, or with
+    signed=True two's-complement values within [-2^(T-1), 2^(T-1) - 1]; duplicates are fine.  The window is the TIGHTEST cyclic one:
+    the distinct bit patterns are sorted, the cycle 0 .. 2^T - 1 .. 0 is cut at its largest gap (on ties: the cut that gives the
+    smallest `lo`), so {-1, 0, 1} of a signed u32 column is 3 bits at lo = 2^32 - 1, not 2^32 bits.  The empty set has bits = 0 and
+    no words.  Bits past `bits` in the last word are clear.  A window of more than `max_bits` bits (the default is a 16-MiB bitmap),
+    or of more than 2^32, raises ValueError: such a set is a join, not a filter.  device: None keeps `words` on the host (a call
+    uploads it to the column's device and keeps it there); a CUDA device puts it there now."""
+    if ty not in _lib.BITS:
+        raise ValueError(f"ty must be one of {list(_lib.TYPES)}")
+    T = _lib.BITS[ty]
+    N, M = 1 << T, (1 << T) - 1
+    p = _member_patterns(ty, members, signed)
+    k = p.size
+    if k == 0:
+        lo, bits = 0, 0
+    elif k == 1:
+        lo, bits = int(p[0]), 1
+    else:
+        gaps = np.concatenate([np.diff(p), (p[:1] - p[-1:]) & np.uint64(M)])   # gaps[i]: from p[i] to its successor on the cycle
+        starts = np.roll(p, -1)[gaps == gaps.max()]                             # the window begins behind a largest gap
+        lo, bits = int(starts.min()), N - int(gaps.max()) + 1
+    if bits > max_bits or bits > min(N, 1 << 32):
+        raise ValueError(f"member_set: the tightest window holds {bits} bits, more than max_bits = {min(max_bits, N, 1 << 32)}")
+    words = np.zeros((bits + 31) // 32, dtype=np.uint32)
+    if k:
+        j = (p - np.uint64(lo)) & np.uint64(M)
+        np.bitwise_or.at(words, (j >> np.uint64(5)).astype(np.int64), np.uint32(1) << (j & np.uint64(31)).astype(np.uint32))
+    ms = MemberSet(ty, lo, bits, words)
+    if device is not None:
+        ms.words = ms.on(device)
+    return ms
+
+
+def _member_args(ty, members, device):
+    """(set_lo, set_bits, set_words) of a call on `device`: `members` a MemberSet of the column's type, or anything member_set takes"""
+    ms = members if isinstance(members, MemberSet) else member_set(ty, members)
+    if ms.ty != ty:
+        raise TypeError(f"the member set is of {ms.ty}, the column of {ty}")
+    return _scalar(ty, ms.lo), ms.bits, ms.on(device).data_ptr() if ms.bits else None
+
+
+def unfor_compare_in_widths(widths, offsets, packed, references, members, negate=False, mask=None, combine="new", output=None, check=True):
+    """FoR.unfor_compare_in over a mixed-width column: membership in `members` (a member_set result, or anything member_set accepts)
+    of the values unfor_pack_widths(widths, offsets, packed, references) yields, inverted by negate=True (NOT IN), joined with the
+    mask so far -- combine "new": the hits themselves (`mask` is ignored), "and" / "or": `mask` & hits / `mask` | hits.  `mask` and
+    the result are CUDA int32 tensors of 32 words per block (unfor_compare_widths' layout); `output` may be `mask` itself (in place).
+    A block whose values all lie outside the set's window, a width-0 block, a block whose `mask` is all zero under "and", and one
+    whose `mask` is all ones under "or" are answered without reading their packed bytes.  The per-block device checks of
+    unfor_compare_widths, with the same contract: a block that fails them is skipped (its 32 mask words are left as they were);
+    `check=True` reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    import torch
+    cb = _range_combine(combine, mask)
+    if cb and _is_torch(mask) and _is_torch(widths) and mask.numel() != 32 * widths.numel():
+        raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block = {32 * widths.numel()}")
+    src = _Arg(packed)
+    ty = src.ty
+    n, lead = _widths_column("unfor_compare_in_widths", src, widths, offsets, references=references)
+    m = _select_mask(src, mask, n) if cb else None
+    out = _consumer_out(src, output, torch.int32, n * 32, "unfor_compare_in_widths")
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_compare_in_widths", src.x.device, *lead, *_member_args(ty, members, src.x.device), int(bool(negate)), cb,
+            m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_compare_in_widths")       # bitpacking.rs:93,126 unreachable!(); :111-113
     return out
 
 

@@ -18,6 +18,7 @@
 #include "fl_consume.hpp"
 #include "fl_for_compare.hpp"
 #include "fl_for_compare_range.hpp"
+#include "fl_for_compare_in.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
@@ -450,6 +451,40 @@ int run_unfor_compare_range(const Column& col, const T* packed, const T* refs, s
     a.mask_in = reinterpret_cast<const char*>(mask_in);
     a.combine = (unsigned)combine;
     return hip_status(for_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// unfor_compare_in: run_unfor_compare_range with the member set's window as the predicate and its bitmap beside it
+// (fl_for_compare_in.hpp, fl_set_decide.hpp).  The same launch shape, the same checks in the same order, the set's own among them:
+// negate and set_bits with combine (FL_ERR_INDEX), set_words with the other pointers (FL_ERR_NULL, FL_ERR_ALIGN; never read when
+// set_bits == 0).  set_bits decides the tier here, once per call: up to SET_REGISTER_BITS the bitmap rides in a VGPR.
+template <typename T>
+int run_unfor_compare_in(const Column& col, const T* packed, const T* refs, size_t ref_stride, T set_lo, uint64_t set_bits,
+                         const uint32_t* set_words, int negate, int combine, const uint32_t* mask_in, size_t n_blocks, uint32_t* mask,
+                         uint32_t* err_flag, void* stream)
+{
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
+    if (combine < FL_MASK_NEW || combine > FL_MASK_OR || negate < 0 || negate > 1 || set_bits > set_max_bits(Elem<T>::BITS)) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
+    else if (!mask_in) return FL_ERR_NULL;
+    if (set_bits == 0) set_words = nullptr;                              // the empty set: never read, never checked
+    else if (!set_words) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs) || !mask) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask) || misaligned(mask_in) || misaligned(set_words)) return FL_ERR_ALIGN;
+    const ForPredicate p = set_window(Elem<T>::BITS, set_lo, set_bits);
+    ForInArgs a;
+    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
+    a.mask = reinterpret_cast<char*>(mask);
+    a.cmp_refs = refs;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = p.none ? 1u : 0u;
+    a.mask_in = reinterpret_cast<const char*>(mask_in);
+    a.combine = (unsigned)combine;
+    a.set_words = set_words;
+    a.set_bytes = (unsigned)(4u * set_word_count(set_bits));
+    a.negate = (unsigned)negate;
+    return hip_status(for_in_launcher<T>(set_bits <= SET_REGISTER_BITS)(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // unfor_compare_columns (fl_for_compare_columns.hpp): two columns of T of the same form, both uniform or both mixed.  The six ops become
@@ -980,6 +1015,19 @@ FL_DEFINE_FOR_COMPARE_RANGE(uint8_t, u8)
 FL_DEFINE_FOR_COMPARE_RANGE(uint16_t, u16)
 FL_DEFINE_FOR_COMPARE_RANGE(uint32_t, u32)
 FL_DEFINE_FOR_COMPARE_RANGE(uint64_t, u64)
+
+#define FL_DEFINE_FOR_COMPARE_IN(T, S)                                                                    \
+    int fl_##S##_unfor_compare_in(unsigned w, const T* in, const T* r, size_t rs, T lo, uint64_t sb, const uint32_t* sw, int ng, int cb, \
+                                  const uint32_t* mi, size_t n, uint32_t* mask, void* s)                  \
+    { FL_DEVICE_TIER(s, in, r, sw, mi, mask); return run_unfor_compare_in<T>({false, w}, in, r, rs, lo, sb, sw, ng, cb, mi, n, mask, nullptr, s); } \
+    int fl_##S##_unfor_compare_in_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, T lo, uint64_t sb, \
+                                         const uint32_t* sw, int ng, int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
+    { FL_DEVICE_TIER(s, w, o, pk, r, sw, mi, mask, ef); return run_unfor_compare_in<T>({true, 0, w, o, pb}, pk, r, rs, lo, sb, sw, ng, cb, mi, n, mask, ef, s); }
+
+FL_DEFINE_FOR_COMPARE_IN(uint8_t, u8)
+FL_DEFINE_FOR_COMPARE_IN(uint16_t, u16)
+FL_DEFINE_FOR_COMPARE_IN(uint32_t, u32)
+FL_DEFINE_FOR_COMPARE_IN(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_COLUMNS(T, S)                                                               \
     int fl_##S##_unfor_compare_columns(unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, size_t brs, \

@@ -13,6 +13,7 @@
 //   17 unfor_aggregate_by (count / sum / min / max per u8 key of the rows a mask keeps, value and key column both FoR-packed; fl_aggregate_by.hpp)
 //   18 unfor_compare_columns (a <op> b between two FoR-packed columns of one type, chained through the mask so far; fl_for_compare_columns.hpp)
 //   19 unfor_aggregate_columns (count / sum / min / max per block of a * b, a + b or a - b between two such columns under a mask; fl_aggregate_columns.hpp)
+//   20 unfor_compare_in (set membership over the same columns: a window of the value domain plus a bitmap, chained through the mask so far; fl_for_compare_in.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -26,6 +27,7 @@
 #include "fl_aggregate_by.hpp"
 #include "fl_for_compare_columns.hpp"
 #include "fl_aggregate_columns.hpp"
+#include "fl_for_compare_in.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -144,7 +146,13 @@ template <> aggregate_by_launch_t aggregate_by_launcher<T>() { return &launch_ag
 template <> for_columns_launch_t for_columns_launcher<T>() { return &launch_block_consumer<T, ForColumnsArgs, k_unfor_compare_columns<T>, false>; }
 #elif FL_FAMILY == 19
 template <> aggregate_columns_launch_t aggregate_columns_launcher<T>() { return &launch_block_consumer<T, AggregateColumnsArgs, k_unfor_aggregate_columns<T>, false>; }
+#elif FL_FAMILY == 20
+template <> for_in_launch_t for_in_launcher<T>(bool register_tier)
+{
+    return register_tier ? &launch_block_consumer<T, ForInArgs, k_unfor_compare_in<T, true>, false>
+                         : &launch_block_consumer<T, ForInArgs, k_unfor_compare_in<T, false>, false>;
+}
 #else
-#error "FL_FAMILY must be 0..6 or 8..19"
+#error "FL_FAMILY must be 0..6 or 8..20"
 #endif
 }  // namespace fl

@@ -666,6 +666,51 @@ FL_DECLARE_AGGREGATE_COLUMNS(uint16_t, u16)
 FL_DECLARE_AGGREGATE_COLUMNS(uint32_t, u32)
 FL_DECLARE_AGGREGATE_COLUMNS(uint64_t, u64)
 
+/*
+ * EXTENSION: SET MEMBERSHIP chained through a mask -- WHERE shipmode IN ('MAIL', 'SHIP'), WHERE size IN (49, 14, 23),
+ * a LIKE evaluated once on a dictionary and probed per row, the probe side of a semi-join -- over the same columns, uniform or mixed
+ * width.  A member set is a WINDOW of the value domain plus a BITMAP: bit j of set_words (bit j % 32 of word j / 32), 0 <= j <
+ * set_bits, says whether (set_lo + j) mod 2^T is a member.  0 <= set_bits <= min(2^T, 2^32); set_words holds ceil(set_bits / 32)
+ * words; bits at positions >= set_bits of the last word are IGNORED (they need not be zero).  set_bits == 0 is the empty set: nothing
+ * is a member, and set_words is not read (it may be NULL).  Defined as the composition (all arithmetic mod 2^T)
+ *     v         = unfor_pack::<W_b>(block b, references[b*reference_stride])[i]                                  (ffor.rs:38-50)
+ *     member(v) = (j := (v - set_lo) mod 2^T) < set_bits  &&  bit j of set_words
+ *     hit[b][i] = member(v) XOR negate                                          -- negate 1: NOT IN
+ *     FL_MASK_NEW: mask[b] = hit[b]   (mask_in ignored, may be NULL)
+ *     FL_MASK_AND: mask[b] = mask_in[b] & hit[b]          FL_MASK_OR: mask[b] = mask_in[b] | hit[b]
+ * A window that wraps past 2^T - 1 is as good as any other; a signed column's set is a window of its two's-complement bit patterns.
+ * Masks have the layout of fl_<ty>_unpack_compare: 32 words per block, bit i % 32 of word b*32 + i/32.  Every valid block's 128 mask
+ * bytes are always written.  `mask` may be the same pointer as `mask_in` (in place); ANY OTHER OVERLAP of the two is the caller's error.
+ * A block is answered without reading its packed bytes when `combine` is AND and its mask_in is all zero, when `combine` is OR and
+ * its mask_in is all ones, when its reference and width put all its values OUTSIDE the window (a miss; all hits under negate), or
+ * when its width is 0 (one bitmap bit decides it).  A window of at most 2048 bits is held in registers (one 256-byte read per
+ * wavefront); a larger one is probed in device memory, one cached 4-byte read per element inside the window.  The mixed-width form
+ * runs the per-block device checks of fl_<ty>_unfor_compare_widths with the same contract -- a failing block is skipped, its
+ * FL_DEVERR_* bit is ORed into *err_flag, its 32 mask words are left as they were -- so all of them can sit in one chain.
+ * width > T is FL_ERR_WIDTH (also for an empty column); a `combine` outside the enum, a `negate` outside {0, 1} or set_bits above
+ * min(2^T, 2^32) FL_ERR_INDEX; n_blocks == 0 FL_OK; mask_in == NULL with AND / OR, set_words == NULL with set_bits > 0, or any other
+ * required pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only when no byte can be read: width 0, or packed_bytes == 0); the
+ * packed column, `mask`, `mask_in` and `set_words` are 16-byte aligned (FL_ERR_ALIGN).
+ * Out of scope: building the bitmap on the device from a key column (a semi-join's build side), windows above 2^32 bits, the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_FOR_COMPARE_IN(T, S)                                                                   \
+    int fl_##S##_unfor_compare_in(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                  T set_lo, uint64_t set_bits, const uint32_t *set_words /* NULL with set_bits 0 */, \
+                                  int negate, int combine, const uint32_t *mask_in /* NULL with FL_MASK_NEW */, \
+                                  size_t n_blocks, uint32_t *mask, void *stream);                         \
+    int fl_##S##_unfor_compare_in_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                         size_t packed_bytes, const T *references, size_t reference_stride, \
+                                         T set_lo, uint64_t set_bits, const uint32_t *set_words /* NULL with set_bits 0 */, \
+                                         int negate, int combine, const uint32_t *mask_in /* NULL with FL_MASK_NEW */, \
+                                         size_t n_blocks, uint32_t *mask, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_FOR_COMPARE_IN(uint8_t, u8)
+FL_DECLARE_FOR_COMPARE_IN(uint16_t, u16)
+FL_DECLARE_FOR_COMPARE_IN(uint32_t, u32)
+FL_DECLARE_FOR_COMPARE_IN(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_compare_widths = fl_##S##_unfor_compare_widths;                  \
         static constexpr auto unfor_compare_range = fl_##S##_unfor_compare_range;                    \
         static constexpr auto unfor_compare_range_widths = fl_##S##_unfor_compare_range_widths;      \
+        static constexpr auto unfor_compare_in = fl_##S##_unfor_compare_in;                          \
+        static constexpr auto unfor_compare_in_widths = fl_##S##_unfor_compare_in_widths;            \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -209,6 +211,12 @@ template <typename T> struct FoR : BitPacking<T> {
                                            fl_mask_combine combine, const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
                                            void* stream = nullptr)
     { detail::check(A::unfor_compare_range((unsigned)width, d_packed, d_refs, ref_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, stream), "unfor_compare_range_device"); }
+    // set membership over the same values: v is a member when j = (v - set_lo) mod 2^T < set_bits and bit j of d_set_words is set
+    // (negate: NOT IN), joined with the mask so far as unfor_compare_range_device does; set_bits == 0 is the empty set
+    static void unfor_compare_in_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, T set_lo,
+                                        std::uint64_t set_bits, const std::uint32_t* d_set_words, bool negate, fl_mask_combine combine,
+                                        const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
+    { detail::check(A::unfor_compare_in((unsigned)width, d_packed, d_refs, ref_stride, set_lo, set_bits, d_set_words, negate ? 1 : 0, (int)combine, d_mask_in, n_blocks, d_mask, stream), "unfor_compare_in_device"); }
     // a <op> b between two FoR-packed columns of T with the same block count (signed: of the two's-complement values), joined with the
     // mask so far as unfor_compare_range_device does; a block pair the references and widths decide reads neither column
     static void unfor_compare_columns_device(std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride, std::size_t width_b,
@@ -473,6 +481,14 @@ inline void unfor_compare_range_widths_device(const std::uint8_t* d_widths, cons
                                               const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
                                               std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_compare_range_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_range_widths"); }
+// ... and set membership chained the same way: mask = [d_mask_in &, |] (value in the member set: a window of set_bits values from set_lo,
+// one bitmap bit each; negate: NOT IN); a block outside the window, or one the mask so far has decided, is not read
+template <typename T>
+inline void unfor_compare_in_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                           const T* d_references, std::size_t reference_stride, T set_lo, std::uint64_t set_bits,
+                                           const std::uint32_t* d_set_words, bool negate, fl_mask_combine combine, const std::uint32_t* d_mask_in,
+                                           std::size_t n_blocks, std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_compare_in_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, set_lo, set_bits, d_set_words, negate ? 1 : 0, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_in_widths"); }
 // ... and a predicate between two mixed-width columns of T with the same block count, a <op> b (signed: of the two's-complement values),
 // chained the same way; both columns get unfor_pack_widths' device checks, a block that fails either keeps its mask words
 template <typename T>
