@@ -135,6 +135,11 @@ _SIGNATURES = (
     # ({vty} as above: these rows' refusals are pinned by tests/test_for_compare_in_cpu.py)
     ("FOR_COMPARE_IN", "fl_{vty}_unfor_compare_in", _I, [_U, _P, _P, _Z, _T, _Q, _P, _I, _I, _P, _Z, _P, _P]),
     ("FOR_COMPARE_IN", "fl_{vty}_unfor_compare_in_widths", _I, [_P, _P, _P, _Z, _P, _Z, _T, _Q, _P, _I, _I, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_AGGREGATE_BY_COLUMNS (device tier): count / sum / min / max per u8 key of a * b, a + b or a - b between two FoR-packed
+    # columns of one element type under a mask ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_by_columns_cpu.py)
+    ("AGGREGATE_BY_COLUMNS", "fl_{vty}_unfor_aggregate_by_columns", _I, [_I, _U, _P, _P, _Z, _U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
+    ("AGGREGATE_BY_COLUMNS", "fl_{vty}_unfor_aggregate_by_columns_widths", _I,
+     [_I, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -204,6 +209,12 @@ def aggregate_columns_symbols():
 def for_compare_in_symbols():
     """The symbols FL_DECLARE_FOR_COMPARE_IN declares: for all four element types the two set-membership entry points."""
     return _symbols("FOR_COMPARE_IN")
+
+
+def aggregate_by_columns_symbols():
+    """The symbols FL_DECLARE_AGGREGATE_BY_COLUMNS declares: for all four value types the two grouped aggregate-of-two-columns entry
+    points."""
+    return _symbols("AGGREGATE_BY_COLUMNS")
 
 
 _LIB = None

@@ -614,6 +614,44 @@ class FoR:
         return _aggregate_call(f"fl_{ty}_unfor_aggregate_columns", sa, n,
                                (ex, width_a, sa.ptr, ra.ptr, stride_a, width_b, sb.ptr, rb.ptr, stride_b), mask, block_aggs, check)
 
+    @staticmethod
+    def unfor_aggregate_by_columns(width_a, a, a_reference, expr, width_b, b, b_reference, key_width, key_packed, key_reference,
+                                   mask=None, n_blocks=None, result=None, check=True):
+        """GROUP BY a u8 key of an expression between two columns: with va = FoR.unfor_pack(width_a, a, a_reference)[i], vb the same
+        of column `b` (the same element type and block count; the widths may differ) and x = va `expr` vb, expr one of '*', '+', '-'
+        (a - b), COUNT / SUM / MIN / MAX of x grouped by the u8 keys FoR.unfor_pack(key_width, key_packed, key_reference) yields in
+        the same rows, where `mask` (the layout unfor_compare returns: a CUDA int32 tensor of 32 words per block; None: everywhere,
+        and no mask is read) has a 1 -- SELECT k, SUM(price * discount) WHERE <mask> GROUP BY k, without materialising any of the
+        three columns.  The values are those of FoR.unfor_aggregate_columns (zero-extended to 64 bits BEFORE the operation: u8 / u16
+        / u32 exact, u64 wraps, a negative difference is its two's-complement pattern, min / max compare the patterns unsigned), the
+        result is that of FoR.unfor_aggregate_by: a CUDA int64[256, 4] tensor (`result` if given), row g = count, sum, min, max of
+        the kept rows whose key is g, (0, 0, 2^64 - 1, 0) for a key that does not occur; every row is written by every call.  A
+        block whose mask is empty is never read; a key width of 0 reads no key byte; a column of width 0 is never read.
+        Deterministic.  Device tier only; no host round trip.  n_blocks is only needed when all three widths are 0 and there is no
+        mask.  SUM(a * (c - b)) per group is c * SUM(a) - SUM(a * b): one more FoR.unfor_aggregate_by launch."""
+        ex = _expr_code(expr)
+        sa, sb, ksrc = _Arg(a), _Arg(b), _Arg(key_packed, "u8")
+        ty = sa.ty
+        if sb.ty != ty:
+            raise TypeError(f"both value columns must have one element type, got {ty} and {sb.ty}")
+        _check_width(ty, width_b, "unfor_aggregate_by_columns")
+        _check_width("u8", key_width, "unfor_aggregate_by_columns")
+        n = _uniform_blocks(sa, width_a, "unfor_aggregate_by_columns", n_blocks, (b if width_b else None, packed_len(ty, width_b)),
+                            (key_packed if key_width else None, packed_len("u8", key_width)), (mask if _is_torch(mask) else None, 32))
+        if _uniform_blocks(sb, width_b, "unfor_aggregate_by_columns", n) != n:
+            raise ValueError(f"column b does not hold column a's {n} blocks")
+        if _uniform_blocks(ksrc, key_width, "unfor_aggregate_by_columns", n) != n:
+            raise ValueError(f"the key column does not hold the value columns' {n} blocks")
+        if not sa.torch:
+            raise TypeError("unfor_aggregate_by_columns is device tier (pass CUDA tensors)")
+        _same_tier(sa, sb, ksrc)
+        ra, stride_a, _ = FoR._ref(sa, ty, a_reference, n)
+        rb, stride_b, _ = FoR._ref(sb, ty, b_reference, n)
+        kaux, kstride, _ = FoR._ref(ksrc, "u8", key_reference, n)
+        return _aggregate_by_call(f"fl_{ty}_unfor_aggregate_by_columns", sa, n,
+                                  (ex, width_a, sa.ptr, ra.ptr, stride_a, width_b, sb.ptr, rb.ptr, stride_b, key_width, ksrc.ptr, kaux.ptr, kstride),
+                                  mask, result, check)
+
 
 class Delta:
     """delta.rs:6-17.  `base` holds LANES = 1024/T elements per block."""
@@ -1194,8 +1232,8 @@ AGGREGATE_BY_GROUPS = 256                   # include/fastlanes_amd.h: one slot 
 
 
 def _aggregate_by_call(name, src, n, lead, mask, result, check):
-    """The part the two grouped-aggregate forms share: mask / result validation, the launch, the error flag.  `lead`: the form's own
-    leading C arguments (the value column's, then the key column's), in front of (mask, n_blocks, result, err_flag, stream)."""
+    """The part the grouped-aggregate forms share: mask / result validation, the launch, the error flag.  `lead`: the form's own
+    leading C arguments (`expr` and the value columns', then the key column's), in front of (mask, n_blocks, result, err_flag, stream)."""
     import torch
     m = _select_mask(src, mask, n) if mask is not None else None
     dev = src.x.device
@@ -1205,7 +1243,7 @@ def _aggregate_by_call(name, src, n, lead, mask, result, check):
         out = _consumer_out(src, result, torch.int64, AGGREGATE_BY_GROUPS * 4, name[name.index("unfor"):]).view(AGGREGATE_BY_GROUPS, 4)
     flag = _Flag(check, dev)
     _launch(name, dev, *lead, m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
-    flag.raise_if_set(name)                 # the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113 -- of either column
+    flag.raise_if_set(name)                 # the mixed form: bitpacking.rs:93,126 unreachable!(); :111-113 -- of any column
     return out
 
 
@@ -1223,6 +1261,30 @@ def unfor_aggregate_by_widths(widths, offsets, packed, references, key_widths, k
     if kn != n:
         raise ValueError(f"the key column holds {kn} blocks, the value column {n}")
     return _aggregate_by_call(f"fl_{src.ty}_unfor_aggregate_by_widths", src, n, (*lead, *klead), mask, result, check)
+
+
+def unfor_aggregate_by_columns_widths(a_widths, a_offsets, a_packed, a_references, expr, b_widths, b_offsets, b_packed, b_references,
+                                      key_widths, key_offsets, key_packed, key_references, mask=None, result=None, check=True):
+    """FoR.unfor_aggregate_by_columns over three mixed-width columns of the same block count: COUNT / SUM / MIN / MAX of va `expr` vb
+    ('*', '+', '-'; both values zero-extended to 64 bits first) of the values unfor_pack_widths yields for column a and for column b
+    (one element type), grouped by the u8 keys unfor_pack_widths(key_widths, key_offsets, key_packed, key_references) yields in the
+    same rows, where `mask` (32 words per block, unfor_compare_widths' layout; None: everywhere) has a 1 -- SELECT k, SUM(price *
+    discount) WHERE <mask> GROUP BY k.  Returns a CUDA int64[256, 4] tensor (`result` if given), row g = count, sum, min, max of key g
+    as FoR.unfor_aggregate_by does.  The per-block device checks of unfor_pack_widths run on ALL THREE columns: a block that fails any
+    contributes nothing and none of its columns is read; `check=True` reads the device error flag back (one sync) and raises,
+    `check=False` stays asynchronous."""
+    ex = _expr_code(expr)
+    sa, sb, ksrc = _Arg(a_packed), _Arg(b_packed), _Arg(key_packed, "u8")
+    if sb.ty != sa.ty:
+        raise TypeError(f"both value columns must have one element type, got {sa.ty} and {sb.ty}")
+    if _numel(b_widths) != _numel(a_widths):
+        raise ValueError(f"column b holds {_numel(b_widths)} blocks, column a {_numel(a_widths)}")
+    if _numel(key_widths) != _numel(a_widths):
+        raise ValueError(f"the key column holds {_numel(key_widths)} blocks, the value columns {_numel(a_widths)}")
+    n, lead_a = _widths_column("unfor_aggregate_by_columns_widths", sa, a_widths, a_offsets, sb, ksrc, references=a_references)
+    _, lead_b = _widths_column("unfor_aggregate_by_columns_widths", sb, b_widths, b_offsets, sa, references=b_references)
+    _, klead = _widths_column("unfor_aggregate_by_columns_widths", ksrc, key_widths, key_offsets, sa, references=key_references)
+    return _aggregate_by_call(f"fl_{sa.ty}_unfor_aggregate_by_columns_widths", sa, n, (ex, *lead_a, *lead_b, *klead), mask, result, check)
 
 
 def for_pack_widths(widths, offsets, input, references, output, check=True):

@@ -50,6 +50,22 @@ __device__ __forceinline__ void group_table_update(BlockAggregate* table, unsign
     __hip_atomic_fetch_max(&s->max, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// the wavefront's table after its last block -> result[256], which holds the identities or other wavefronts' flushes
+__device__ __forceinline__ void group_table_flush(const BlockAggregate* table, BlockAggregate* result, unsigned lane)
+{
+    wave_lds_fence();
+    for (unsigned g = lane; g < AGGREGATE_BY_GROUPS; g += 64u) {
+        const BlockAggregate s = table[g];
+        if (s.count != 0ull) {                                              // as k_aggregate_reduce: four 64-bit vector atomics
+            BlockAggregate* out = result + g;
+            __hip_atomic_fetch_add(&out->count, s.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&out->sum, s.sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_min(&out->min, s.min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_max(&out->max, s.max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 // a block's loads, issued and possibly still in flight
 template <typename T> struct GroupBlockLoads {
     BlockLoads<T> v;
@@ -178,17 +194,7 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by(AggregateByArgs a)
         aggregate_by_block<T>(a, blk, cur, lds_all, lane);
         cur = nxt;
     }
-    wave_lds_fence();
-    for (unsigned g = lane; g < AGGREGATE_BY_GROUPS; g += 64u) {
-        const BlockAggregate s = table[g];
-        if (s.count != 0ull) {                                              // as k_aggregate_reduce: four 64-bit vector atomics
-            BlockAggregate* out = a.result + g;
-            __hip_atomic_fetch_add(&out->count, s.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&out->sum, s.sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_min(&out->min, s.min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_max(&out->max, s.max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    group_table_flush(table, a.result, lane);
 }
 
 // Resident wavefronts per CU wanted; what fits the CU's LDS (17 / 13 / 11 / 10 KiB per wavefront for u64 / u32 / u16 / u8) caps it.
@@ -196,21 +202,24 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by(AggregateByArgs a)
 constexpr int AGGREGATE_BY_WAVES_PER_CU = 16;
 
 // The grid is what is resident at once, at most one wavefront per block; a wavefront's run is the column divided evenly, and at least
-// val.bpw blocks (the A/B tools' and the tests' blocks-per-wavefront override; 0 = none).  The caller has launched k_aggregate_by_init.
-template <typename T>
-hipError_t launch_aggregate_by(const AggregateByArgs& a0, int waves, hipStream_t s)
+// `bpw` blocks (the A/B tools' and the tests' blocks-per-wavefront override; 0 = none).  The caller has launched k_aggregate_by_init.
+// KERNEL takes Args, which has a `run` field; LDS is its request per wavefront.
+template <auto KERNEL, unsigned LDS, typename Args>
+hipError_t launch_group_runs(Args a, uint64_t n, unsigned bpw, int waves, hipStream_t s)
 {
-    if (a0.val.n_blocks == 0) return hipSuccess;
-    AggregateByArgs a = a0;
-    const uint64_t n = a.val.n_blocks;
-    constexpr unsigned lds = aggregate_by_lds<T>();
-    static_assert(lds <= 64 * 1024, "the default dynamic-LDS limit");
+    if (n == 0) return hipSuccess;
+    static_assert(LDS <= 64 * 1024, "the default dynamic-LDS limit");
     unsigned grid = n < (1ull << 30) ? (unsigned)n : 1u << 30;
-    if (hipError_t e = persistent_grid<k_unfor_aggregate_by<T>>(lds, waves > 0 ? 4 * waves : AGGREGATE_BY_WAVES_PER_CU, grid); e != hipSuccess) return e;
+    if (hipError_t e = persistent_grid<KERNEL>(LDS, waves > 0 ? 4 * waves : AGGREGATE_BY_WAVES_PER_CU, grid); e != hipSuccess) return e;
     a.run = (n + grid - 1) / grid;
-    if (a.run < a.val.bpw) a.run = a.val.bpw;
-    FL_LAUNCH((k_unfor_aggregate_by<T>), dim3(grid), dim3(64), lds, s, a);
+    if (a.run < bpw) a.run = bpw;
+    FL_LAUNCH(KERNEL, dim3(grid), dim3(64), LDS, s, a);
     return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_aggregate_by(const AggregateByArgs& a, int waves, hipStream_t s)
+{
+    return launch_group_runs<k_unfor_aggregate_by<T>, aggregate_by_lds<T>()>(a, a.val.n_blocks, a.val.bpw, waves, s);
 }
 
 typedef hipError_t (*aggregate_by_launch_t)(const AggregateByArgs&, int waves, hipStream_t);

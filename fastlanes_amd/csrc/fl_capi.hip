@@ -19,6 +19,7 @@
 #include "fl_for_compare.hpp"
 #include "fl_for_compare_range.hpp"
 #include "fl_for_compare_in.hpp"
+#include "fl_aggregate_by_columns.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
@@ -616,6 +617,41 @@ int run_unfor_aggregate_by(const Column& col, const T* packed, const T* refs, si
     return hip_status(aggregate_by_launcher<T>()(a, sh.waves, s));
 }
 
+// unfor_aggregate_by_columns (fl_aggregate_by_columns.hpp): two value columns of T met under `expr` and a u8 key column, all three of
+// the same form, uniform or mixed; a block that fails any column's checks contributes nothing.  The checks of run_unfor_aggregate_by
+// in its order, `expr` where run_unfor_aggregate_columns judges it; `result` and the persistent grid as run_unfor_aggregate_by has them.
+template <typename T>
+int run_unfor_aggregate_by_columns(int expr, const Column& cola, const T* a_packed, const T* a_refs, size_t a_ref_stride, const Column& colb,
+                                   const T* b_packed, const T* b_refs, size_t b_ref_stride, const Column& kcol, const uint8_t* keys,
+                                   const uint8_t* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, void* result,
+                                   uint32_t* err_flag, void* stream)
+{
+    if ((!cola.mixed && over_width<T>(cola.width)) || (!colb.mixed && over_width<T>(colb.width)) || (!kcol.mixed && over_width<uint8_t>(kcol.width)))
+        return FL_ERR_WIDTH;
+    if (!expr_valid(expr)) return FL_ERR_INDEX;
+    if (!result) return FL_ERR_NULL;
+    if (n_blocks && (!block_consumer_column(cola, a_packed, a_refs) || !block_consumer_column(colb, b_packed, b_refs) ||
+                     !block_consumer_column(kcol, keys, key_refs)))
+        return FL_ERR_NULL;
+    if ((n_blocks && (misaligned(a_packed) || misaligned(b_packed) || misaligned(keys) || misaligned(mask))) || misaligned(result)) return FL_ERR_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipError_t e = launch_aggregate_by_init(static_cast<BlockAggregate*>(result), s); e != hipSuccess || n_blocks == 0) return hip_status(e);
+    const WaveShape sh = with_policy({0, 0u, 0u});
+    AggregateByColumnsArgs a;
+    uint32_t* ef = cola.mixed ? err_flag : nullptr;
+    widths_args<T>(a.a, cola, a_packed, nullptr, nullptr, a_ref_stride, ef, n_blocks, sh);
+    widths_args<T>(a.b, colb, b_packed, nullptr, nullptr, b_ref_stride, ef, n_blocks, sh);
+    widths_args<uint8_t>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, ef, n_blocks, sh);
+    a.a_refs = a_refs;
+    a.b_refs = b_refs;
+    a.key_refs = key_refs;
+    a.mask = mask;
+    a.result = static_cast<BlockAggregate*>(result);
+    a.run = 0;
+    a.expr = (unsigned)expr;
+    return hip_status(aggregate_by_columns_launcher<T>()(a, sh.waves, s));
+}
+
 template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n, uint8_t* widths, void* s)
 {
     if (n == 0) return FL_OK;
@@ -1003,7 +1039,30 @@ FL_DEFINE_AGGREGATE_BY(uint16_t, u16)
 FL_DEFINE_AGGREGATE_BY(uint32_t, u32)
 FL_DEFINE_AGGREGATE_BY(uint64_t, u64)
 
-#define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                                 \
+#define FL_DEFINE_AGGREGATE_BY_COLUMNS(T, S)                                                              \
+    int fl_##S##_unfor_aggregate_by_columns(int ex, unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, \
+                                            size_t brs, unsigned kw, const uint8_t* k, const uint8_t* kr, size_t krs, const uint32_t* mask, \
+                                            size_t n, void* res, uint32_t* ef, void* s)                   \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, a, ar, b, br, k, kr, mask, res, ef);                                            \
+        return run_unfor_aggregate_by_columns<T>(ex, {false, wa}, a, ar, ars, {false, wb}, b, br, brs, {false, kw}, k, kr, krs, mask, n, res, ef, s); \
+    }                                                                                                     \
+    int fl_##S##_unfor_aggregate_by_columns_widths(int ex, const uint8_t* aw, const uint64_t* ao, const T* a, size_t ab, const T* ar, size_t ars, \
+                                                   const uint8_t* bw, const uint64_t* bo, const T* b, size_t bb, const T* br, size_t brs, \
+                                                   const uint8_t* kw, const uint64_t* ko, const uint8_t* k, size_t kb, const uint8_t* kr, \
+                                                   size_t krs, const uint32_t* mask, size_t n, void* res, uint32_t* ef, void* s) \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, aw, ao, a, ar, bw, bo, b, br, kw, ko, k, kr, mask, res, ef);                    \
+        return run_unfor_aggregate_by_columns<T>(ex, {true, 0, aw, ao, ab}, a, ar, ars, {true, 0, bw, bo, bb}, b, br, brs, {true, 0, kw, ko, kb}, k, \
+                                                 kr, krs, mask, n, res, ef, s);                           \
+    }
+
+FL_DEFINE_AGGREGATE_BY_COLUMNS(uint8_t, u8)
+FL_DEFINE_AGGREGATE_BY_COLUMNS(uint16_t, u16)
+FL_DEFINE_AGGREGATE_BY_COLUMNS(uint32_t, u32)
+FL_DEFINE_AGGREGATE_BY_COLUMNS(uint64_t, u64)
+
+#define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                               \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \
                                      uint32_t* mask, void* s)                                             \
     { FL_DEVICE_TIER(s, in, r, mi, mask); return run_unfor_compare_range<T>({false, w}, in, r, rs, lo, hi, cb, mi, n, mask, nullptr, s); } \

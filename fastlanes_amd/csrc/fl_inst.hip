@@ -14,6 +14,7 @@
 //   18 unfor_compare_columns (a <op> b between two FoR-packed columns of one type, chained through the mask so far; fl_for_compare_columns.hpp)
 //   19 unfor_aggregate_columns (count / sum / min / max per block of a * b, a + b or a - b between two such columns under a mask; fl_aggregate_columns.hpp)
 //   20 unfor_compare_in (set membership over the same columns: a window of the value domain plus a bitmap, chained through the mask so far; fl_for_compare_in.hpp)
+//   21 unfor_aggregate_by_columns (count / sum / min / max per u8 key of a * b, a + b or a - b between two such columns under a mask, all three columns FoR-packed; fl_aggregate_by_columns.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -28,6 +29,7 @@
 #include "fl_for_compare_columns.hpp"
 #include "fl_aggregate_columns.hpp"
 #include "fl_for_compare_in.hpp"
+#include "fl_aggregate_by_columns.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -152,7 +154,9 @@ template <> for_in_launch_t for_in_launcher<T>(bool register_tier)
     return register_tier ? &launch_block_consumer<T, ForInArgs, k_unfor_compare_in<T, true>, false>
                          : &launch_block_consumer<T, ForInArgs, k_unfor_compare_in<T, false>, false>;
 }
+#elif FL_FAMILY == 21
+template <> aggregate_by_columns_launch_t aggregate_by_columns_launcher<T>() { return &launch_aggregate_by_columns<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..20"
+#error "FL_FAMILY must be 0..6 or 8..21"
 #endif
 }  // namespace fl

@@ -711,6 +711,64 @@ FL_DECLARE_FOR_COMPARE_IN(uint16_t, u16)
 FL_DECLARE_FOR_COMPARE_IN(uint32_t, u32)
 FL_DECLARE_FOR_COMPARE_IN(uint64_t, u64)
 
+/*
+ * EXTENSION (the two aggregates above composed): COUNT / SUM / MIN / MAX of ARITHMETIC BETWEEN TWO COLUMNS, GROUPED BY A KEY --
+ * SELECT k, SUM(price * discount) WHERE <mask> GROUP BY k (TPC-H Q1), revenue per status, a dot product per category -- over two
+ * FoR-packed VALUE columns `a` and `b` of the SAME element type T and one FoR-packed KEY column of type u8, all three with the same
+ * n_blocks, all three uniform width (the first form; the three widths may differ) or all three mixed width (the _widths form).  None
+ * of the three columns is materialised.  Defined as the composition
+ *     va  = unfor_pack::<WA_b>(a block b, a_references[b*a_reference_stride])[i]                                     (ffor.rs:38-50)
+ *     vb  = unfor_pack::<WB_b>(b block b, b_references[b*b_reference_stride])[i]
+ *     key = unfor_pack::<KW_b>(key block b, key_references[b*key_reference_stride])[i]                           (u8, wrapping add)
+ *     x   = (zext64(va) o zext64(vb)) mod 2^64              o = `expr`, an fl_expr: FL_EXPR_MUL a * b, FL_EXPR_ADD a + b, FL_EXPR_SUB a - b
+ *     result[g] = combine over all (b, i) with mask bit (b, i) set and key == g of {1, x, x, x}                      g = 0 .. 255
+ * `combine`, the identity {0, 0, UINT64_MAX, 0}, the 256 fl_block_aggregate slots of `result`, the mask layout and mask == NULL are
+ * exactly those of fl_<ty>_unfor_aggregate_by; the value semantics are exactly those of fl_<ty>_unfor_aggregate_columns: the values
+ * are widened to 64 bits BEFORE the operation, so u8 / u16 / u32 results are exact and u64 ones wrap; a difference below zero is its
+ * two's-complement 64-bit pattern (read the SUM as int64_t), and MIN AND MAX COMPARE THE PATTERNS AS UNSIGNED NUMBERS.  Every slot is
+ * written by every call; a group that does not occur, and every group when n_blocks == 0, receives the identity.  A reference stride
+ * of 0 broadcasts the column's references[0].  The result is deterministic.  Asynchronous on `stream`, no allocation, no
+ * synchronisation, no scratch memory: the launches of fl_<ty>_unfor_aggregate_by.
+ * A block whose mask is empty is never read; a key block of width 0 is answered from its reference, no key byte is read, and its two
+ * value blocks are aggregated exactly as fl_<ty>_unfor_aggregate_columns does (two widths of 0 read nothing at all); a value column
+ * whose width is 0 in a block is never read there.  The mixed-width form runs the per-block device checks of
+ * fl_<ty>_unfor_pack_widths on ALL THREE columns: a block that fails any of them raises its FL_DEVERR_* bits in *err_flag and
+ * contributes NOTHING; none of its columns is read.
+ * width_a or width_b > T, or key_width > 8, is FL_ERR_WIDTH (also for an empty column); an `expr` outside fl_expr FL_ERR_INDEX;
+ * `result` is required by every call, the other pointers when n_blocks > 0 (FL_ERR_NULL) -- a packed pointer may be NULL only when no
+ * byte of it can be read (its width is 0, or its packed bytes are 0; `mask` may be NULL); the packed columns, `keys`, `mask` and
+ * `result` are 16-byte aligned (FL_ERR_ALIGN).
+ * SUM(a * (c - b)) per group for a constant c is c * SUM(a) - SUM(a * b): TPC-H Q1's sum_disc_price takes two launches, this one for
+ * SUM(price * discount) and fl_<ty>_unfor_aggregate_by for SUM(price).
+ * Out of scope: keys wider than u8, a second key column, more than one expression per launch, three-column products, constants inside
+ * the expression, signed (sign-extending) columns, Delta columns, the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_AGGREGATE_BY_COLUMNS(T, S)                                                             \
+    int fl_##S##_unfor_aggregate_by_columns(int expr, unsigned width_a, const T *a, const T *a_references, \
+                                            size_t a_reference_stride, unsigned width_b, const T *b,      \
+                                            const T *b_references, size_t b_reference_stride,             \
+                                            unsigned key_width, const uint8_t *keys, const uint8_t *key_references, \
+                                            size_t key_reference_stride, const uint32_t *mask /* may be NULL */, \
+                                            size_t n_blocks, void *result /* fl_block_aggregate[256] */,  \
+                                            uint32_t *err_flag, void *stream);                            \
+    int fl_##S##_unfor_aggregate_by_columns_widths(int expr, const uint8_t *a_widths, const uint64_t *a_offsets, const T *a_packed, \
+                                                   size_t a_packed_bytes, const T *a_references, size_t a_reference_stride, \
+                                                   const uint8_t *b_widths, const uint64_t *b_offsets, const T *b_packed, \
+                                                   size_t b_packed_bytes, const T *b_references, size_t b_reference_stride, \
+                                                   const uint8_t *key_widths, const uint64_t *key_offsets, \
+                                                   const uint8_t *keys, size_t keys_bytes,                \
+                                                   const uint8_t *key_references, size_t key_reference_stride, \
+                                                   const uint32_t *mask /* may be NULL */, size_t n_blocks, \
+                                                   void *result /* fl_block_aggregate[256] */,            \
+                                                   uint32_t *err_flag, void *stream);
+
+FL_DECLARE_AGGREGATE_BY_COLUMNS(uint8_t, u8)
+FL_DECLARE_AGGREGATE_BY_COLUMNS(uint16_t, u16)
+FL_DECLARE_AGGREGATE_BY_COLUMNS(uint32_t, u32)
+FL_DECLARE_AGGREGATE_BY_COLUMNS(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

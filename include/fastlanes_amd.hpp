@@ -75,6 +75,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_aggregate_by_widths = fl_##S##_unfor_aggregate_by_widths;        \
         static constexpr auto unfor_aggregate_columns = fl_##S##_unfor_aggregate_columns;            \
         static constexpr auto unfor_aggregate_columns_widths = fl_##S##_unfor_aggregate_columns_widths; \
+        static constexpr auto unfor_aggregate_by_columns = fl_##S##_unfor_aggregate_by_columns;      \
+        static constexpr auto unfor_aggregate_by_columns_widths = fl_##S##_unfor_aggregate_by_columns_widths; \
         static constexpr auto unpack_mixed = fl_##S##_unpack_mixed;                                  \
         static constexpr auto pack_mixed = fl_##S##_pack_mixed;                                      \
         static constexpr auto unpack_widths = fl_##S##_unpack_widths;                                \
@@ -250,6 +252,14 @@ template <typename T> struct FoR : BitPacking<T> {
                                                const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_block_aggs,
                                                std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
     { detail::check(A::unfor_aggregate_columns((int)expr, (unsigned)width_a, d_a, d_a_refs, a_ref_stride, (unsigned)width_b, d_b, d_b_refs, b_ref_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_columns_device"); }
+    // the same expression grouped by a FoR-packed u8 key column of the same block count: d_result[g] (256 slots, all written by every call)
+    // = count / sum / min / max of a * b, a + b or a - b over the kept rows whose key is g; none of the three columns is materialised
+    static void unfor_aggregate_by_columns_device(fl_expr expr, std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride,
+                                                  std::size_t width_b, const T* d_b, const T* d_b_refs, std::size_t b_ref_stride,
+                                                  std::size_t key_width, const std::uint8_t* d_keys, const std::uint8_t* d_key_refs,
+                                                  std::size_t key_ref_stride, const std::uint32_t* d_mask, std::size_t n_blocks,
+                                                  fl_block_aggregate* d_result, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_aggregate_by_columns((int)expr, (unsigned)width_a, d_a, d_a_refs, a_ref_stride, (unsigned)width_b, d_b, d_b_refs, b_ref_stride, (unsigned)key_width, d_keys, d_key_refs, key_ref_stride, d_mask, n_blocks, d_result, d_err_flag, stream), "unfor_aggregate_by_columns_device"); }
 };
 
 // delta.rs:6-17
@@ -536,6 +546,19 @@ inline void unfor_aggregate_columns_widths_device(fl_expr expr, const std::uint8
                                                   const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_block_aggs,
                                                   std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_aggregate_columns_widths((int)expr, d_a_widths, d_a_offsets, d_a_packed, a_packed_bytes, d_a_references, a_reference_stride, d_b_widths, d_b_offsets, d_b_packed, b_packed_bytes, d_b_references, b_reference_stride, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "unfor_aggregate_columns_widths"); }
+// unfor_aggregate_by_columns over three mixed-width columns with the same block count (a and b of T, the keys u8): d_result[g] (256 slots) =
+// count / sum / min / max of a * b, a + b or a - b per key; all three columns get unfor_pack_widths' device checks, a block that fails any
+// contributes nothing
+template <typename T>
+inline void unfor_aggregate_by_columns_widths_device(fl_expr expr, const std::uint8_t* d_a_widths, const std::uint64_t* d_a_offsets, const T* d_a_packed,
+                                                     std::size_t a_packed_bytes, const T* d_a_references, std::size_t a_reference_stride,
+                                                     const std::uint8_t* d_b_widths, const std::uint64_t* d_b_offsets, const T* d_b_packed,
+                                                     std::size_t b_packed_bytes, const T* d_b_references, std::size_t b_reference_stride,
+                                                     const std::uint8_t* d_key_widths, const std::uint64_t* d_key_offsets, const std::uint8_t* d_keys,
+                                                     std::size_t keys_bytes, const std::uint8_t* d_key_references, std::size_t key_reference_stride,
+                                                     const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_result,
+                                                     std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_aggregate_by_columns_widths((int)expr, d_a_widths, d_a_offsets, d_a_packed, a_packed_bytes, d_a_references, a_reference_stride, d_b_widths, d_b_offsets, d_b_packed, b_packed_bytes, d_b_references, b_reference_stride, d_key_widths, d_key_offsets, d_keys, keys_bytes, d_key_references, key_reference_stride, d_mask, n_blocks, d_result, d_err_flag, stream), "unfor_aggregate_by_columns_widths"); }
 // per-block aggregates -> the column's: counts and sums added (wrapping), the smallest min, the largest max; no blocks: the identity
 inline void aggregate_reduce_device(const fl_block_aggregate* d_block_aggs, std::size_t n_blocks, fl_block_aggregate* d_result, void* stream = nullptr)
 { detail::check(fl_aggregate_reduce(d_block_aggs, n_blocks, d_result, stream), "aggregate_reduce"); }
