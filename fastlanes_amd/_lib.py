@@ -140,6 +140,10 @@ _SIGNATURES = (
     ("AGGREGATE_BY_COLUMNS", "fl_{vty}_unfor_aggregate_by_columns", _I, [_I, _U, _P, _P, _Z, _U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_BY_COLUMNS", "fl_{vty}_unfor_aggregate_by_columns_widths", _I,
      [_I, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_SET_BUILD (device tier): the member set of the values a mask keeps, ORed into a window's bitmap -- the build side of
+    # unfor_compare_in ({vty} as above: these rows' refusals are pinned by tests/test_set_build_cpu.py)
+    ("SET_BUILD", "fl_{vty}_unfor_set_build", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P]),
+    ("SET_BUILD", "fl_{vty}_unfor_set_build_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -215,6 +219,11 @@ def aggregate_by_columns_symbols():
     """The symbols FL_DECLARE_AGGREGATE_BY_COLUMNS declares: for all four value types the two grouped aggregate-of-two-columns entry
     points."""
     return _symbols("AGGREGATE_BY_COLUMNS")
+
+
+def set_build_symbols():
+    """The symbols FL_DECLARE_SET_BUILD declares: for all four element types the two member-set build entry points."""
+    return _symbols("SET_BUILD")
 
 
 _LIB = None

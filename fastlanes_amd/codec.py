@@ -489,6 +489,30 @@ class FoR:
         return out
 
     @staticmethod
+    def unfor_set_build(width, packed, reference, lo, bits, mask=None, into=None, n_blocks=None):
+        """The member set of a column's values, built on the device (the build side of the semi-join unfor_compare_in probes): every
+        v = FoR.unfor_pack(width, block b, reference)[i] in a row `mask` keeps (a CUDA int32 tensor of 32 words per block, the layout
+        unfor_compare returns; None: every row) sets bit j = (v - lo) mod 2^T of the set when j < bits, and is counted as outside
+        the window otherwise.  Returns (MemberSet, stats): the set (ty, lo, bits, words on the column's device) is usable in
+        unfor_compare_in* as it stands; stats is a CUDA int64[2] tensor holding uint64 bits: kept rows inside, kept rows outside.
+        `into`: a device MemberSet of the same ty, lo and bits, updated IN PLACE and returned (the union; stats counts this call
+        alone).  A block whose mask is empty, a block outside the window and a width-0 block are answered without reading their
+        packed bytes.  Device tier only.  n_blocks is only needed for width == 0 without a mask."""
+        import torch
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_set_build is device tier (pass CUDA tensors)")
+        n = _uniform_blocks(src, width, "unfor_set_build", n_blocks, (mask if _is_torch(mask) else None, 32))
+        m = _select_mask(src, mask, n) if mask is not None else None
+        ms = _set_build_target(ty, lo, bits, into, src.x.device)
+        stats = torch.zeros(2, dtype=torch.int64, device=src.x.device)
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        _launch(f"fl_{ty}_unfor_set_build", src.x.device, width, src.ptr, aux.ptr, stride, m.ptr if m is not None and n else None, n,
+                _scalar(ty, ms.lo), ms.bits, ms.words.data_ptr() if ms.bits else None, stats.data_ptr())
+        return ms, stats
+
+    @staticmethod
     def unfor_compare_columns(width_a, a, a_reference, op, width_b, b, b_reference, *, signed=False, mask=None, combine="new", n_blocks=None,
                               output=None):
         """A predicate between two columns, chained through a mask: with va = FoR.unfor_pack(width_a, a block, a_reference)[i] and vb
@@ -1072,6 +1096,113 @@ def unfor_compare_in_widths(widths, offsets, packed, references, members, negate
             m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_unfor_compare_in_widths")       # bitpacking.rs:93,126 unreachable!(); :111-113
     return out
+
+
+def column_window(ty, widths, references, signed=False, max_bits=1 << 27):
+    """(lo, bits) of the smallest NON-CYCLIC window that covers every value a FoR-packed column of element type `ty` can hold: block b
+    with reference r and width w holds values in [r, r + 2^w - 1], and the window is [min r, max (r + 2^w - 1)] -- computed from the
+    per-block metadata alone (`widths` one u8 per block, `references` one scalar per block or a single one, broadcast), with torch on
+    the tensors' device (one sync) or with numpy.  signed=True orders the bit patterns as two's complement, so a column around 0 gets
+    a window that starts at a negative value's pattern; `lo` is always the bit pattern unfor_set_build and member sets take.  A block
+    whose range passes the end of that order (r + 2^w - 1 > 2^T - 1, or above the largest signed value) has no such window: ValueError
+    -- pass an explicit window then.  A window of more than `max_bits` bits (or of more than 2^32) raises ValueError too.  An empty
+    column gives (0, 0).
+    unfor_set_build with column_window of the PROBE column builds exactly the bits a probe of that column can ever ask for: a key of
+    the build side outside it can match no probe row (it is counted in stats[1]), and unfor_compare_in decides every probe block
+    against the same window."""
+    if ty not in _lib.BITS:
+        raise ValueError(f"ty must be one of {list(_lib.TYPES)}")
+    T = _lib.BITS[ty]
+    if _is_torch(widths) != _is_torch(references):
+        raise TypeError("widths and references must both be torch tensors or both be numpy arrays")
+    if _is_torch(widths):
+        import torch
+        if references.device != widths.device:
+            raise ValueError(f"tensors live on different devices ({widths.device} vs {references.device})")
+        if widths.element_size() != 1 or references.element_size() * 8 != T or references.dtype.is_floating_point:
+            raise TypeError(f"widths must be a uint8 tensor and references a {ty} tensor, got {widths.dtype} and {references.dtype}")
+        signed_view = {8: torch.int8, 16: torch.int16, 32: torch.int32, 64: torch.int64}[T]
+        wv = widths.reshape(-1).view(torch.uint8).to(torch.int64)
+        rv = references.contiguous().reshape(-1).view(signed_view).to(torch.int64)
+    else:
+        wa, ra = np.asarray(widths), np.ascontiguousarray(references)
+        if wa.dtype.kind not in "ui" or wa.dtype.itemsize != 1 or ra.dtype.kind not in "ui" or ra.dtype.itemsize * 8 != T:
+            raise TypeError(f"widths must be a uint8 array and references a {ty} array, got {wa.dtype} and {ra.dtype}")
+        wv, rv = wa.reshape(-1).view(np.uint8).astype(np.int64), ra.reshape(-1).view(f"i{T // 8}").astype(np.int64)
+    if len(rv) not in (1, len(wv)):
+        raise ValueError("references must hold one scalar per block (or exactly one, broadcast)")
+    if len(wv) == 0:
+        return 0, 0
+    if int(wv.max()) > T:
+        raise ValueError(f"column_window: a width above {T}")
+    # k: the patterns' rank in the chosen order, held in an int64 -- for T = 64 shifted down by 2^63 (order-preserving)
+    sign = 1 << (T - 1)
+    if T < 64:
+        k = (rv & ((1 << T) - 1)) ^ (sign if signed else 0)
+        top, shift = (1 << T) - 1, 0
+    else:
+        k = rv if signed else rv ^ (-sign)                                 # (-2^63: the sign bit of an int64)
+        top, shift = sign - 1, sign
+    one = wv * 0 + 1
+    span = (one << (wv - (wv == 64) * 1)) - 1                              # 2^w - 1; w = 64 (2^64 - 1) is judged on its own
+    full = wv == 64
+    wraps = bool(((k > top - span) | (full & (k != -sign))).any())
+    if wraps:
+        raise ValueError("column_window: a block's range passes the end of the "
+                         f"{'signed' if signed else 'unsigned'} order; pass an explicit window (lo, bits)")
+    lo_k, hi_k = int(k.min()), top if bool(full.any()) else int((k + span).max())
+    bits = hi_k - lo_k + 1
+    if bits > max_bits or bits > min(1 << T, 1 << 32):
+        raise ValueError(f"column_window: the window holds {bits} bits, more than max_bits = {min(max_bits, 1 << T, 1 << 32)}")
+    return ((lo_k + shift) ^ (sign if signed else 0)) & ((1 << T) - 1), bits
+
+
+def _set_build_target(ty, lo, bits, into, device):
+    """The MemberSet a set_build call ORs into: `into` (a device MemberSet of the same ty, lo and bits on `device`) or a fresh, zeroed one"""
+    import torch
+    T = _lib.BITS[ty]
+    lo, bits = int(lo) & ((1 << T) - 1), int(bits)
+    if bits < 0 or bits > min(1 << T, 1 << 32):
+        raise ValueError(f"bits must lie in [0, {min(1 << T, 1 << 32)}], got {bits}")
+    if into is None:
+        return MemberSet(ty, lo, bits, torch.zeros((bits + 31) // 32, dtype=torch.int32, device=device))
+    if not isinstance(into, MemberSet) or not (_is_torch(into.words) and into.words.is_cuda):
+        raise TypeError("into must be a MemberSet whose words live on the device (an earlier unfor_set_build result, or member_set(..., device=...))")
+    if into.ty != ty:
+        raise TypeError(f"into is a member set of {into.ty}, the column of {ty}")
+    if (into.lo, into.bits) != (lo, bits):
+        raise ValueError(f"into has the window (lo={into.lo}, bits={into.bits}), the call (lo={lo}, bits={bits})")
+    if into.words.device != device:
+        raise ValueError(f"tensors live on different devices ({device} vs {into.words.device})")
+    if into.words.numel() != (bits + 31) // 32 or into.words.element_size() != 4 or not into.words.is_contiguous():
+        raise ValueError(f"into.words must hold {(bits + 31) // 32} contiguous 4-byte words")
+    return into
+
+
+def unfor_set_build_widths(widths, offsets, packed, references, lo, bits, mask=None, into=None, check=True):
+    """FoR.unfor_set_build over a mixed-width column: the member set of the values unfor_pack_widths(widths, offsets, packed,
+    references) yields where `mask` (32 words per block, unfor_compare_widths' layout; None: everywhere) has a 1, inside the window of
+    `bits` bit patterns from `lo` (fl.column_window of the probe column gives the window a probe can ever ask for) -- the build side of
+    the semi-join unfor_compare_in probes: `m` of any predicate chain on table A -> unfor_set_build_widths(A's key column, lo, bits,
+    mask=m) -> unfor_compare_in_widths(B's key column, set), both key columns packed.  Returns (MemberSet, stats): the set's `words`
+    are a CUDA int32 tensor on the column's device, usable in unfor_compare_in* as it stands; stats is a CUDA int64[2] tensor holding
+    uint64 bits: kept rows inside the window, kept rows outside it.  `into`: a device MemberSet of the same ty, lo and bits that is
+    updated IN PLACE and returned -- the union over several columns or masks (stats counts this call alone).  A block whose mask is
+    empty, a block outside the window and a width-0 block are answered without reading their packed bytes.  The per-block device
+    checks of unfor_compare_widths: a block that fails them contributes nothing; `check=True` reads the device error flag back (one
+    sync) and raises, `check=False` stays asynchronous."""
+    import torch
+    src = _Arg(packed)
+    ty = src.ty
+    n, lead = _widths_column("unfor_set_build_widths", src, widths, offsets, references=references)
+    m = _select_mask(src, mask, n) if mask is not None else None
+    ms = _set_build_target(ty, lo, bits, into, src.x.device)
+    stats = torch.zeros(2, dtype=torch.int64, device=src.x.device)
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_set_build_widths", src.x.device, *lead, m.ptr if m is not None and n else None, n, _scalar(ty, ms.lo), ms.bits,
+            ms.words.data_ptr() if ms.bits else None, stats.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_set_build_widths")        # bitpacking.rs:93,126 unreachable!(); :111-113
+    return ms, stats
 
 
 def unfor_compare_columns_widths(a_widths, a_offsets, a_packed, a_references, op, b_widths, b_offsets, b_packed, b_references, *,

@@ -20,6 +20,7 @@
 #include "fl_for_compare_range.hpp"
 #include "fl_for_compare_in.hpp"
 #include "fl_aggregate_by_columns.hpp"
+#include "fl_set_build.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
@@ -29,6 +30,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <new>
 
 namespace {
@@ -486,6 +488,53 @@ int run_unfor_compare_in(const Column& col, const T* packed, const T* refs, size
     a.set_bytes = (unsigned)(4u * set_word_count(set_bits));
     a.negate = (unsigned)negate;
     return hip_status(for_in_launcher<T>(set_bits <= SET_REGISTER_BITS)(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// unfor_set_build (fl_set_build.hpp): the member set unfor_compare_in probes, built from a column under a mask.  The window's checks are
+// run_unfor_compare_in's, in its order: the width; set_bits (FL_ERR_INDEX); the empty column; set_words (never touched when set_bits
+// == 0) and the column's pointers (FL_ERR_NULL); alignment, set_words and stats included.  `mask` and `stats` may be NULL.  set_bits
+// decides the tier here, once per call (fl_set_build_map.hpp: set_build_lds_tier).  The memory tier ships SET_BUILD_MEMORY_TIER; the
+// timing tool measures the other variant beside it through the environment variable FL_INTERNAL_SET_BUILD_VARIANT (1: one atomic per
+// element, 2: test before set; read on every memory-tier call, bits identical either way).  The persistent grid takes the policy's
+// waves and blocks per wavefront as run_unfor_aggregate_by does.
+constexpr int SET_BUILD_MEMORY_TIER = SETB_MEM_TEST;
+inline int set_build_tier(uint64_t set_bits)
+{
+    if (set_build_lds_tier(set_bits)) return SETB_LDS;
+    if (const char* v = std::getenv("FL_INTERNAL_SET_BUILD_VARIANT")) {
+        if (v[0] == '1' && !v[1]) return SETB_MEM;
+        if (v[0] == '2' && !v[1]) return SETB_MEM_TEST;
+    }
+    return SET_BUILD_MEMORY_TIER;
+}
+template <typename T>
+int run_unfor_set_build(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, T set_lo,
+                        uint64_t set_bits, uint32_t* set_words, uint64_t* stats, uint32_t* err_flag, void* stream)
+{
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
+    if (set_bits > set_max_bits(Elem<T>::BITS)) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (set_bits == 0) set_words = nullptr;                              // the empty window: never touched, never checked
+    else if (!set_words) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs)) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask) || misaligned(set_words) || misaligned(stats)) return FL_ERR_ALIGN;
+    const ForPredicate p = set_window(Elem<T>::BITS, set_lo, set_bits);
+    const WaveShape sh = with_policy({0, 0u, 0u});
+    SetBuildArgs a;
+    widths_args<T>(a.col, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    a.refs = refs;
+    a.mask = mask;
+    a.set_words = set_words;
+    a.stats = stats;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = p.none ? 1u : 0u;
+    a.n_words = (unsigned)set_word_count(set_bits);
+    a.last_mask = set_build_last_word_mask(set_bits);
+    a.run = 0;
+    const set_build_launch_t fn = set_build_launcher<T>(set_build_tier(set_bits));
+    if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
+    return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // unfor_compare_columns (fl_for_compare_columns.hpp): two columns of T of the same form, both uniform or both mixed.  The six ops become
@@ -1061,6 +1110,19 @@ FL_DEFINE_AGGREGATE_BY_COLUMNS(uint8_t, u8)
 FL_DEFINE_AGGREGATE_BY_COLUMNS(uint16_t, u16)
 FL_DEFINE_AGGREGATE_BY_COLUMNS(uint32_t, u32)
 FL_DEFINE_AGGREGATE_BY_COLUMNS(uint64_t, u64)
+
+#define FL_DEFINE_SET_BUILD(T, S)                                                                         \
+    int fl_##S##_unfor_set_build(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, T lo, uint64_t sb, \
+                                 uint32_t* sw, uint64_t* st, void* s)                                     \
+    { FL_DEVICE_TIER(s, in, r, mask, sw, st); return run_unfor_set_build<T>({false, w}, in, r, rs, mask, n, lo, sb, sw, st, nullptr, s); } \
+    int fl_##S##_unfor_set_build_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
+                                        size_t n, T lo, uint64_t sb, uint32_t* sw, uint64_t* st, uint32_t* ef, void* s) \
+    { FL_DEVICE_TIER(s, w, o, pk, r, mask, sw, st, ef); return run_unfor_set_build<T>({true, 0, w, o, pb}, pk, r, rs, mask, n, lo, sb, sw, st, ef, s); }
+
+FL_DEFINE_SET_BUILD(uint8_t, u8)
+FL_DEFINE_SET_BUILD(uint16_t, u16)
+FL_DEFINE_SET_BUILD(uint32_t, u32)
+FL_DEFINE_SET_BUILD(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                               \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \

@@ -15,6 +15,7 @@
 //   19 unfor_aggregate_columns (count / sum / min / max per block of a * b, a + b or a - b between two such columns under a mask; fl_aggregate_columns.hpp)
 //   20 unfor_compare_in (set membership over the same columns: a window of the value domain plus a bitmap, chained through the mask so far; fl_for_compare_in.hpp)
 //   21 unfor_aggregate_by_columns (count / sum / min / max per u8 key of a * b, a + b or a - b between two such columns under a mask, all three columns FoR-packed; fl_aggregate_by_columns.hpp)
+//   22 unfor_set_build (the member set of the values a mask keeps of such a column, ORed into a window's bitmap: the build side of unfor_compare_in; fl_set_build.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -30,6 +31,7 @@
 #include "fl_aggregate_columns.hpp"
 #include "fl_for_compare_in.hpp"
 #include "fl_aggregate_by_columns.hpp"
+#include "fl_set_build.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -156,7 +158,16 @@ template <> for_in_launch_t for_in_launcher<T>(bool register_tier)
 }
 #elif FL_FAMILY == 21
 template <> aggregate_by_columns_launch_t aggregate_by_columns_launcher<T>() { return &launch_aggregate_by_columns<T>; }
+#elif FL_FAMILY == 22
+template <> set_build_launch_t set_build_launcher<T>(int tier)
+{
+    if constexpr (sizeof(T) >= 4) {                         // a window above SET_BUILD_LDS_BITS: only the wide types have one
+        if (tier == SETB_MEM) return &launch_set_build<T, SETB_MEM>;
+        if (tier == SETB_MEM_TEST) return &launch_set_build<T, SETB_MEM_TEST>;
+    }
+    return tier == SETB_LDS ? &launch_set_build<T, SETB_LDS> : nullptr;
+}
 #else
-#error "FL_FAMILY must be 0..6 or 8..21"
+#error "FL_FAMILY must be 0..6 or 8..22"
 #endif
 }  // namespace fl

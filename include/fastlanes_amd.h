@@ -691,7 +691,8 @@ FL_DECLARE_AGGREGATE_COLUMNS(uint64_t, u64)
  * min(2^T, 2^32) FL_ERR_INDEX; n_blocks == 0 FL_OK; mask_in == NULL with AND / OR, set_words == NULL with set_bits > 0, or any other
  * required pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only when no byte can be read: width 0, or packed_bytes == 0); the
  * packed column, `mask`, `mask_in` and `set_words` are 16-byte aligned (FL_ERR_ALIGN).
- * Out of scope: building the bitmap on the device from a key column (a semi-join's build side), windows above 2^32 bits, the host tier.
+ * The bitmap is built on the device from a key column by fl_<ty>_unfor_set_build below (a semi-join's build side).
+ * Out of scope: windows above 2^32 bits, the host tier.
  * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
  * are pinned surfaces.)
  */
@@ -768,6 +769,49 @@ FL_DECLARE_AGGREGATE_BY_COLUMNS(uint8_t, u8)
 FL_DECLARE_AGGREGATE_BY_COLUMNS(uint16_t, u16)
 FL_DECLARE_AGGREGATE_BY_COLUMNS(uint32_t, u32)
 FL_DECLARE_AGGREGATE_BY_COLUMNS(uint64_t, u64)
+
+/*
+ * EXTENSION: BUILD A MEMBER SET on the device -- the build side of the semi-join whose probe side is
+ * fl_<ty>_unfor_compare_in: WHERE o_orderkey IN (SELECT l_orderkey FROM lineitem WHERE l_commitdate < l_receiptdate), every EXISTS.
+ * The mask of any predicate chain on one table becomes a member set that filters another; both key columns stay packed.  Defined as
+ * the composition (all arithmetic mod 2^T)
+ *     for every block b, every i in 0..1023 with bit i of block b of `mask` set (mask == NULL: every i):
+ *         v = unfor_pack::<W_b>(block b, references[b*reference_stride])[i]                                      (ffor.rs:38-50)
+ *         j = (v - set_lo) mod 2^T
+ *         if j < set_bits:  bit j of set_words |= 1;  inserted += 1          else:  outside += 1
+ *     stats[0] += inserted;  stats[1] += outside                            -- stats: DEVICE uint64[2], may be NULL
+ * set_lo, set_bits (0 <= set_bits <= min(2^T, 2^32)) and the layout of set_words (ceil(set_bits / 32) words, bit j % 32 of word j / 32)
+ * are exactly those of fl_<ty>_unfor_compare_in: the output is passed to it as it stands.  THE CALL ORs AND ADDS, IT NEVER CLEARS: the
+ * caller zeroes set_words and stats, or passes the result of an earlier call -- the union over several columns or masks is several
+ * calls.  Bits at positions >= set_bits of the last word are never changed.  set_bits == 0 reads no packed byte, touches no word
+ * (set_words may be NULL) and counts every kept row as outside.  OR and integer add commute: the result is bitwise reproducible.
+ * `mask` has the layout of fl_<ty>_unpack_compare, 32 words per block.  A block whose mask is empty, a block whose reference and width
+ * put all its values outside the window and a width-0 block (one bit) are answered without reading their packed bytes.  A window of at
+ * most 65536 bits is built in a private bitmap per wavefront and ORed into set_words once per wavefront; a larger one takes one device
+ * atomic per kept element inside the window.  The mixed-width form runs the per-block device checks of fl_<ty>_unfor_compare_widths:
+ * a failing block is skipped, its FL_DEVERR_* bit is ORed into *err_flag, it contributes nothing to the bitmap or to stats.
+ * width > T is FL_ERR_WIDTH (also for an empty column); set_bits above min(2^T, 2^32) FL_ERR_INDEX; n_blocks == 0 FL_OK (nothing is
+ * touched); set_words == NULL with set_bits > 0, or any required column pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only
+ * when no byte can be read: width 0, or packed_bytes == 0); the packed column, `mask`, `set_words` and `stats` are 16-byte aligned
+ * (FL_ERR_ALIGN).
+ * Out of scope: Delta columns, the host tier, windows above 2^32 bits, counting bitmaps (multiplicities), keys of another type than
+ * the probe column.
+ */
+#define FL_DECLARE_SET_BUILD(T, S)                                                                        \
+    int fl_##S##_unfor_set_build(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                 const uint32_t *mask /* NULL: every row */, size_t n_blocks,             \
+                                 T set_lo, uint64_t set_bits, uint32_t *set_words /* NULL with set_bits 0 */, \
+                                 uint64_t *stats /* may be NULL */, void *stream);                        \
+    int fl_##S##_unfor_set_build_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,  \
+                                        size_t packed_bytes, const T *references, size_t reference_stride, \
+                                        const uint32_t *mask /* NULL: every row */, size_t n_blocks,      \
+                                        T set_lo, uint64_t set_bits, uint32_t *set_words /* NULL with set_bits 0 */, \
+                                        uint64_t *stats /* may be NULL */, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_SET_BUILD(uint8_t, u8)
+FL_DECLARE_SET_BUILD(uint16_t, u16)
+FL_DECLARE_SET_BUILD(uint32_t, u32)
+FL_DECLARE_SET_BUILD(uint64_t, u64)
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_compare_range_widths = fl_##S##_unfor_compare_range_widths;      \
         static constexpr auto unfor_compare_in = fl_##S##_unfor_compare_in;                          \
         static constexpr auto unfor_compare_in_widths = fl_##S##_unfor_compare_in_widths;            \
+        static constexpr auto unfor_set_build = fl_##S##_unfor_set_build;                            \
+        static constexpr auto unfor_set_build_widths = fl_##S##_unfor_set_build_widths;              \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -219,6 +221,13 @@ template <typename T> struct FoR : BitPacking<T> {
                                         std::uint64_t set_bits, const std::uint32_t* d_set_words, bool negate, fl_mask_combine combine,
                                         const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
     { detail::check(A::unfor_compare_in((unsigned)width, d_packed, d_refs, ref_stride, set_lo, set_bits, d_set_words, negate ? 1 : 0, (int)combine, d_mask_in, n_blocks, d_mask, stream), "unfor_compare_in_device"); }
+    // the member set unfor_compare_in_device probes, built from the same values: every value v of a row d_mask keeps (nullptr: every
+    // row) sets bit j = (v - set_lo) mod 2^T of d_set_words when j < set_bits; d_stats (nullptr: not counted) += {kept rows inside the
+    // window, kept rows outside}.  ORs and adds, never clears: zero d_set_words and d_stats first, or pass an earlier call's
+    static void unfor_set_build_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
+                                       std::size_t n_blocks, T set_lo, std::uint64_t set_bits, std::uint32_t* d_set_words,
+                                       std::uint64_t* d_stats = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_set_build((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, set_lo, set_bits, d_set_words, d_stats, stream), "unfor_set_build_device"); }
     // a <op> b between two FoR-packed columns of T with the same block count (signed: of the two's-complement values), joined with the
     // mask so far as unfor_compare_range_device does; a block pair the references and widths decide reads neither column
     static void unfor_compare_columns_device(std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride, std::size_t width_b,
@@ -499,6 +508,14 @@ inline void unfor_compare_in_widths_device(const std::uint8_t* d_widths, const s
                                            const std::uint32_t* d_set_words, bool negate, fl_mask_combine combine, const std::uint32_t* d_mask_in,
                                            std::size_t n_blocks, std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_compare_in_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, set_lo, set_bits, d_set_words, negate ? 1 : 0, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_in_widths"); }
+// ... and the member set such a probe takes, built from a mixed-width column under a mask (the build side of a semi-join): bit
+// (v - set_lo) mod 2^T of d_set_words |= 1 for every kept value v inside the window, d_stats += {inside, outside}; never clears
+template <typename T>
+inline void unfor_set_build_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                          const T* d_references, std::size_t reference_stride, const std::uint32_t* d_mask, std::size_t n_blocks,
+                                          T set_lo, std::uint64_t set_bits, std::uint32_t* d_set_words, std::uint64_t* d_stats = nullptr,
+                                          std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_set_build_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, set_lo, set_bits, d_set_words, d_stats, d_err_flag, stream), "unfor_set_build_widths"); }
 // ... and a predicate between two mixed-width columns of T with the same block count, a <op> b (signed: of the two's-complement values),
 // chained the same way; both columns get unfor_pack_widths' device checks, a block that fails either keeps its mask words
 template <typename T>
