@@ -144,6 +144,11 @@ _SIGNATURES = (
     # unfor_compare_in ({vty} as above: these rows' refusals are pinned by tests/test_set_build_cpu.py)
     ("SET_BUILD", "fl_{vty}_unfor_set_build", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P]),
     ("SET_BUILD", "fl_{vty}_unfor_set_build_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P]),
+    # FL_DECLARE_AGGREGATE_BY_WINDOW (device tier): COUNT / SUM / MIN / MAX per key of a dense window, value and key column of one type,
+    # accumulated into the caller's four arrays ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_by_window_cpu.py)
+    ("AGGREGATE_BY_WINDOW", "fl_{vty}_unfor_aggregate_by_window", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
+    ("AGGREGATE_BY_WINDOW", "fl_{vty}_unfor_aggregate_by_window_widths", _I,
+     [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -224,6 +229,11 @@ def aggregate_by_columns_symbols():
 def set_build_symbols():
     """The symbols FL_DECLARE_SET_BUILD declares: for all four element types the two member-set build entry points."""
     return _symbols("SET_BUILD")
+
+
+def aggregate_by_window_symbols():
+    """The symbols FL_DECLARE_AGGREGATE_BY_WINDOW declares: for all four element types the two windowed group-by entry points."""
+    return _symbols("AGGREGATE_BY_WINDOW")
 
 
 _LIB = None

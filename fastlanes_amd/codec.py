@@ -513,6 +513,48 @@ class FoR:
         return ms, stats
 
     @staticmethod
+    def unfor_aggregate_by_window(width, packed, reference, key_width, key_packed, key_reference, lo, n_groups, mask=None,
+                                  what=("count", "sum"), into=None, n_blocks=None):
+        """GROUP BY a key column of the value column's own type inside a dense window of the key domain: every row `mask` keeps (a
+        CUDA int32 tensor of 32 words per block, the layout unfor_compare returns; None: every row) with the key k =
+        FoR.unfor_pack(key_width, key_packed, key_reference)[i] updates slot j = (k - lo) mod 2^T of the arrays `what` names
+        ("count", "sum", "min", "max") with the value FoR.unfor_pack(width, packed, reference)[i] when j < n_groups, and is counted
+        as outside the window otherwise -- without materialising either column.  Returns (GroupTable, stats): the table's arrays
+        are CUDA int64[n_groups] tensors holding uint64 bits (None for what is not named), freshly initialised to the identities
+        0 / 0 / 2^64 - 1 / 0; stats is a CUDA int64[2] tensor holding uint64 bits: kept rows inside, kept rows outside.  `into`: a
+        GroupTable of the same ty, lo, n_groups and arrays, updated IN PLACE and returned (stats counts this call alone).
+        packed=None is the COUNT-only form: the key column stands in both places and what must be ("count",); without "sum", "min"
+        and "max" the value column is never read.  A block whose mask is empty and a key block outside the window read neither
+        column; a width-0 key block reads no key byte.  Device tier only.  n_blocks is only needed when both widths are 0 and
+        there is no mask."""
+        import torch
+        names = _window_what(what)
+        if packed is None:
+            if names != ("count",):
+                raise ValueError('packed=None is the COUNT-only form: what must be ("count",)')
+            width, packed, reference = key_width, key_packed, key_reference
+        src, ksrc = _Arg(packed), _Arg(key_packed)
+        ty = src.ty
+        if ksrc.ty != ty:
+            raise TypeError(f"the key column must have the value column's element type, got {ksrc.ty} and {ty}")
+        if not src.torch:
+            raise TypeError("unfor_aggregate_by_window is device tier (pass CUDA tensors)")
+        _same_tier(src, ksrc)
+        _check_width(ty, key_width, "unfor_aggregate_by_window")
+        n = _uniform_blocks(src, width, "unfor_aggregate_by_window", n_blocks, (key_packed if key_width else None, packed_len(ty, key_width)),
+                            (mask if _is_torch(mask) else None, 32))
+        if _uniform_blocks(ksrc, key_width, "unfor_aggregate_by_window", n) != n:
+            raise ValueError(f"the key column does not hold the value column's {n} blocks")
+        m = _select_mask(src, mask, n) if mask is not None else None
+        table = _group_table_target(ty, lo, n_groups, names, into, src.x.device)
+        stats = torch.zeros(2, dtype=torch.int64, device=src.x.device)
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        kaux, kstride, _ = FoR._ref(ksrc, ty, key_reference, n)
+        _launch(f"fl_{ty}_unfor_aggregate_by_window", src.x.device, width, src.ptr, aux.ptr, stride, key_width, ksrc.ptr, kaux.ptr, kstride,
+                m.ptr if m is not None and n else None, n, _scalar(ty, table.lo), table.n_groups, *table._pointers(), stats.data_ptr())
+        return table, stats
+
+    @staticmethod
     def unfor_compare_columns(width_a, a, a_reference, op, width_b, b, b_reference, *, signed=False, mask=None, combine="new", n_blocks=None,
                               output=None):
         """A predicate between two columns, chained through a mask: with va = FoR.unfor_pack(width_a, a block, a_reference)[i] and vb
@@ -1203,6 +1245,111 @@ def unfor_set_build_widths(widths, offsets, packed, references, lo, bits, mask=N
             ms.words.data_ptr() if ms.bits else None, stats.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_unfor_set_build_widths")        # bitpacking.rs:93,126 unreachable!(); :111-113
     return ms, stats
+
+
+class GroupTable:
+    """The table unfor_aggregate_by_window* accumulates into: the key column's element type `ty`, the window (`lo`, `n_groups`) and, for
+    slot j = (key - lo) mod 2^T, `counts`, `sums`, `mins`, `maxs`: CUDA int64[n_groups] tensors holding uint64 bits, or None for an
+    array the call does not maintain."""
+    __slots__ = ("ty", "lo", "n_groups", "counts", "sums", "mins", "maxs")
+
+    def __init__(self, ty, lo, n_groups, counts=None, sums=None, mins=None, maxs=None):
+        self.ty, self.lo, self.n_groups, self.counts, self.sums, self.mins, self.maxs = ty, lo, n_groups, counts, sums, mins, maxs
+
+    def __iter__(self):
+        return iter((self.ty, self.lo, self.n_groups, self.counts, self.sums, self.mins, self.maxs))
+
+    def __repr__(self):
+        return f"GroupTable({self.ty}, lo={self.lo}, n_groups={self.n_groups}, what={self.what()})"
+
+    def what(self):
+        """the names of the arrays the table holds, in the order count, sum, min, max"""
+        return tuple(name for name, t in zip(_WINDOW_WHAT, (self.counts, self.sums, self.mins, self.maxs)) if t is not None)
+
+    def _pointers(self):
+        return tuple(t.data_ptr() if t is not None and self.n_groups else None for t in (self.counts, self.sums, self.mins, self.maxs))
+
+
+_WINDOW_WHAT = ("count", "sum", "min", "max")
+
+
+def _window_what(what):
+    """`what` of unfor_aggregate_by_window*: a tuple or list of distinct names out of count, sum, min, max -> in that order"""
+    if isinstance(what, str) or not isinstance(what, (tuple, list)):
+        raise TypeError(f"what must be a tuple of names out of {_WINDOW_WHAT}, got {what!r}")
+    if any(w not in _WINDOW_WHAT for w in what) or len(set(what)) != len(what):
+        raise ValueError(f"what must hold distinct names out of {_WINDOW_WHAT}, got {tuple(what)!r}")
+    return tuple(w for w in _WINDOW_WHAT if w in what)
+
+
+def _group_table_target(ty, lo, n_groups, names, into, device):
+    """The GroupTable a call accumulates into: `into` (the same ty, lo, n_groups and arrays, on `device`) or a fresh one of identities"""
+    import torch
+    T = _lib.BITS[ty]
+    lo, n_groups = int(lo) & ((1 << T) - 1), int(n_groups)
+    if n_groups < 0 or n_groups > min(1 << T, 1 << 32):
+        raise ValueError(f"n_groups must lie in [0, {min(1 << T, 1 << 32)}], got {n_groups}")
+    if into is None:
+        fresh = {"count": 0, "sum": 0, "min": -1, "max": 0}                 # (-1: the bits of 2^64 - 1)
+        return GroupTable(ty, lo, n_groups, *(torch.full((n_groups,), fresh[w], dtype=torch.int64, device=device) if w in names else None
+                                              for w in _WINDOW_WHAT))
+    if not isinstance(into, GroupTable):
+        raise TypeError("into must be a GroupTable (an earlier unfor_aggregate_by_window result)")
+    if (into.ty, into.lo, into.n_groups) != (ty, lo, n_groups):
+        raise ValueError(f"into is a table of {into.ty} with the window (lo={into.lo}, n_groups={into.n_groups}), the call of {ty} with "
+                         f"(lo={lo}, n_groups={n_groups})")
+    if into.what() != names:
+        raise ValueError(f"into holds the arrays {into.what()}, the call maintains {names}")
+    for t in (into.counts, into.sums, into.mins, into.maxs):
+        if t is None:
+            continue
+        if not (_is_torch(t) and t.is_cuda):
+            raise TypeError("into's arrays must be CUDA tensors")
+        if t.device != device:
+            raise ValueError(f"tensors live on different devices ({device} vs {t.device})")
+        if t.numel() != n_groups or t.element_size() != 8 or t.dtype.is_floating_point or not t.is_contiguous():
+            raise ValueError(f"into's arrays must hold {n_groups} contiguous 8-byte integers")
+    return into
+
+
+def unfor_aggregate_by_window_widths(widths, offsets, packed, references, key_widths, key_offsets, key_packed, key_references, lo, n_groups,
+                                     mask=None, what=("count", "sum"), into=None, check=True):
+    """FoR.unfor_aggregate_by_window over two mixed-width columns of one element type and block count: GROUP BY a wide key inside a
+    dense window -- SELECT l_orderkey, SUM(l_quantity) ... GROUP BY l_orderkey.  Every row `mask` keeps (32 words per block,
+    unfor_compare_widths' layout; None: every row) with the key k = unfor_pack_widths(key_widths, key_offsets, key_packed,
+    key_references)[i] updates slot j = (k - lo) mod 2^T of the arrays `what` names ("count", "sum", "min", "max") with the value
+    unfor_pack_widths(widths, offsets, packed, references)[i] when j < n_groups, and is counted as outside otherwise; (lo, n_groups)
+    of a key column comes from fl.column_window(ty, key_widths, key_references).  Returns (GroupTable, stats): the table's arrays are
+    CUDA int64[n_groups] tensors holding uint64 bits (None for what is not named), freshly initialised to the identities 0 / 0 /
+    2^64 - 1 / 0; stats is a CUDA int64[2] tensor holding uint64 bits: kept rows inside the window, kept rows outside it.  `into`: a
+    GroupTable of the same ty, lo, n_groups and arrays that is updated IN PLACE and returned -- several masks, columns or shards of
+    one table (stats counts this call alone).  packed=None (widths, offsets and references are then ignored) is the COUNT-only form:
+    the key column stands in both places and what must be ("count",); without "sum", "min" and "max" the value column is never read.
+    A block whose mask is empty and a key block outside the window read neither column; a width-0 key block reads no key byte.  The
+    per-block device checks of unfor_pack_widths run on BOTH columns: a block that fails either contributes nothing; `check=True`
+    reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    import torch
+    names = _window_what(what)
+    if packed is None:
+        if names != ("count",):
+            raise ValueError('packed=None is the COUNT-only form: what must be ("count",)')
+        widths, offsets, packed, references = key_widths, key_offsets, key_packed, key_references
+    src, ksrc = _Arg(packed), _Arg(key_packed)
+    ty = src.ty
+    if ksrc.ty != ty:
+        raise TypeError(f"the key column must have the value column's element type, got {ksrc.ty} and {ty}")
+    n, lead = _widths_column("unfor_aggregate_by_window_widths", src, widths, offsets, ksrc, references=references)
+    kn, klead = _widths_column("unfor_aggregate_by_window_widths", ksrc, key_widths, key_offsets, src, references=key_references)
+    if kn != n:
+        raise ValueError(f"the key column holds {kn} blocks, the value column {n}")
+    m = _select_mask(src, mask, n) if mask is not None else None
+    table = _group_table_target(ty, lo, n_groups, names, into, src.x.device)
+    stats = torch.zeros(2, dtype=torch.int64, device=src.x.device)
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_aggregate_by_window_widths", src.x.device, *lead, *klead, m.ptr if m is not None and n else None, n,
+            _scalar(ty, table.lo), table.n_groups, *table._pointers(), stats.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_aggregate_by_window_widths")   # bitpacking.rs:93,126 unreachable!(); :111-113
+    return table, stats
 
 
 def unfor_compare_columns_widths(a_widths, a_offsets, a_packed, a_references, op, b_widths, b_offsets, b_packed, b_references, *,

@@ -21,6 +21,7 @@
 #include "fl_for_compare_in.hpp"
 #include "fl_aggregate_by_columns.hpp"
 #include "fl_set_build.hpp"
+#include "fl_aggregate_by_window.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by.hpp"
@@ -533,6 +534,68 @@ int run_unfor_set_build(const Column& col, const T* packed, const T* refs, size_
     a.last_mask = set_build_last_word_mask(set_bits);
     a.run = 0;
     const set_build_launch_t fn = set_build_launcher<T>(set_build_tier(set_bits));
+    if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
+    return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// unfor_aggregate_by_window (fl_aggregate_by_window.hpp): a value column and a key column of T of the same form, both uniform or both
+// mixed, grouped inside the window [key_lo, key_lo + n_groups - 1] into the caller's four arrays.  One validator, one builder.
+// The validator's order is run_unfor_set_build's: the widths; n_groups (FL_ERR_INDEX); the empty column; the columns' pointers
+// (FL_ERR_NULL; the four arrays, `mask` and `stats` may be NULL); alignment, the arrays and stats included.  An empty window touches no
+// array: the builder drops them, so they are neither maintained nor checked.
+struct WindowArrays {
+    uint64_t *counts, *sums, *mins, *maxs, *stats;
+};
+template <typename T>
+int aggregate_by_window_refusal(const Column& col, const T*& packed, const T* refs, const Column& kcol, const T*& keys, const T* key_refs,
+                                const uint32_t* mask, size_t n_blocks, uint64_t n_groups, WindowArrays& t)
+{
+    if ((!col.mixed && over_width<T>(col.width)) || (!kcol.mixed && over_width<T>(kcol.width))) return FL_ERR_WIDTH;
+    if (n_groups > aggregate_by_window_max_groups(Elem<T>::BITS)) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (n_groups == 0) t.counts = t.sums = t.mins = t.maxs = nullptr;    // the empty window: never touched, never checked
+    if (!block_consumer_column(col, packed, refs) || !block_consumer_column(kcol, keys, key_refs)) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(keys) || misaligned(mask) || misaligned(t.counts) || misaligned(t.sums) || misaligned(t.mins) ||
+        misaligned(t.maxs) || misaligned(t.stats))
+        return FL_ERR_ALIGN;
+    return FL_OK;
+}
+template <typename T>
+AggregateByWindowArgs aggregate_by_window_args(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
+                                               const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
+                                               uint64_t n_groups, const WindowArrays& t, uint32_t* err_flag, const WaveShape& sh)
+{
+    const ForPredicate p = set_window(Elem<T>::BITS, key_lo, n_groups);
+    AggregateByWindowArgs a;
+    widths_args<T>(a.val, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    widths_args<T>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    a.val_refs = refs;
+    a.key_refs = key_refs;
+    a.mask = mask;
+    a.counts = t.counts;
+    a.sums = t.sums;
+    a.mins = t.mins;
+    a.maxs = t.maxs;
+    a.stats = t.stats;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = p.none ? 1u : 0u;
+    a.need_values = t.sums || t.mins || t.maxs ? 1u : 0u;
+    a.n_slots = aggregate_by_window_lds_tier(n_groups) ? (unsigned)n_groups : 0u;
+    a.run = 0;
+    return a;
+}
+template <typename T>
+int run_unfor_aggregate_by_window(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
+                                  const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo, uint64_t n_groups,
+                                  WindowArrays t, uint32_t* err_flag, void* stream)
+{
+    if (const int rc = aggregate_by_window_refusal<T>(col, packed, refs, kcol, keys, key_refs, mask, n_blocks, n_groups, t); rc != FL_OK || n_blocks == 0)
+        return rc;
+    const WaveShape sh = with_policy({0, 0u, 0u});
+    const AggregateByWindowArgs a =
+        aggregate_by_window_args<T>(col, packed, refs, ref_stride, kcol, keys, key_refs, key_ref_stride, mask, n_blocks, key_lo, n_groups, t, err_flag, sh);
+    const aggregate_by_window_launch_t fn = aggregate_by_window_launcher<T>(aggregate_by_window_lds_tier(n_groups) ? AGGW_LDS : AGGW_MEM);
     if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
     return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
@@ -1123,6 +1186,29 @@ FL_DEFINE_SET_BUILD(uint8_t, u8)
 FL_DEFINE_SET_BUILD(uint16_t, u16)
 FL_DEFINE_SET_BUILD(uint32_t, u32)
 FL_DEFINE_SET_BUILD(uint64_t, u64)
+
+#define FL_DEFINE_AGGREGATE_BY_WINDOW(T, S)                                                               \
+    int fl_##S##_unfor_aggregate_by_window(unsigned w, const T* in, const T* r, size_t rs, unsigned kw, const T* k, const T* kr, size_t krs, \
+                                           const uint32_t* mask, size_t n, T lo, uint64_t ng, uint64_t* cn, uint64_t* sm, uint64_t* mn, \
+                                           uint64_t* mx, uint64_t* st, void* s)                           \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, in, r, k, kr, mask, cn, sm, mn, mx, st);                                        \
+        return run_unfor_aggregate_by_window<T>({false, w}, in, r, rs, {false, kw}, k, kr, krs, mask, n, lo, ng, {cn, sm, mn, mx, st}, nullptr, s); \
+    }                                                                                                     \
+    int fl_##S##_unfor_aggregate_by_window_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, \
+                                                  const uint8_t* kw, const uint64_t* ko, const T* k, size_t kb, const T* kr, size_t krs, \
+                                                  const uint32_t* mask, size_t n, T lo, uint64_t ng, uint64_t* cn, uint64_t* sm, uint64_t* mn, \
+                                                  uint64_t* mx, uint64_t* st, uint32_t* ef, void* s)      \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, w, o, pk, r, kw, ko, k, kr, mask, cn, sm, mn, mx, st, ef);                      \
+        return run_unfor_aggregate_by_window<T>({true, 0, w, o, pb}, pk, r, rs, {true, 0, kw, ko, kb}, k, kr, krs, mask, n, lo, ng, \
+                                                {cn, sm, mn, mx, st}, ef, s);                             \
+    }
+
+FL_DEFINE_AGGREGATE_BY_WINDOW(uint8_t, u8)
+FL_DEFINE_AGGREGATE_BY_WINDOW(uint16_t, u16)
+FL_DEFINE_AGGREGATE_BY_WINDOW(uint32_t, u32)
+FL_DEFINE_AGGREGATE_BY_WINDOW(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                               \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \

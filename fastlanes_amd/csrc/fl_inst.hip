@@ -16,6 +16,7 @@
 //   20 unfor_compare_in (set membership over the same columns: a window of the value domain plus a bitmap, chained through the mask so far; fl_for_compare_in.hpp)
 //   21 unfor_aggregate_by_columns (count / sum / min / max per u8 key of a * b, a + b or a - b between two such columns under a mask, all three columns FoR-packed; fl_aggregate_by_columns.hpp)
 //   22 unfor_set_build (the member set of the values a mask keeps of such a column, ORed into a window's bitmap: the build side of unfor_compare_in; fl_set_build.hpp)
+//   23 unfor_aggregate_by_window (count / sum / min / max per key of a dense window of the key domain, value and key column FoR-packed and of one type, accumulated into the caller's arrays; fl_aggregate_by_window.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -32,6 +33,7 @@
 #include "fl_for_compare_in.hpp"
 #include "fl_aggregate_by_columns.hpp"
 #include "fl_set_build.hpp"
+#include "fl_aggregate_by_window.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -167,7 +169,15 @@ template <> set_build_launch_t set_build_launcher<T>(int tier)
     }
     return tier == SETB_LDS ? &launch_set_build<T, SETB_LDS> : nullptr;
 }
+#elif FL_FAMILY == 23
+template <> aggregate_by_window_launch_t aggregate_by_window_launcher<T>(int tier)
+{
+    if constexpr (sizeof(T) >= 2) {                         // a window above AGGREGATE_BY_WINDOW_LDS_GROUPS: u8 has none
+        if (tier == AGGW_MEM) return &launch_aggregate_by_window<T, AGGW_MEM>;
+    }
+    return tier == AGGW_LDS ? &launch_aggregate_by_window<T, AGGW_LDS> : nullptr;
+}
 #else
-#error "FL_FAMILY must be 0..6 or 8..22"
+#error "FL_FAMILY must be 0..6 or 8..23"
 #endif
 }  // namespace fl

@@ -813,6 +813,69 @@ FL_DECLARE_SET_BUILD(uint16_t, u16)
 FL_DECLARE_SET_BUILD(uint32_t, u32)
 FL_DECLARE_SET_BUILD(uint64_t, u64)
 
+/*
+ * EXTENSION: GROUP BY A WIDE KEY inside a dense window of the key domain -- SELECT l_orderkey, SUM(l_quantity) ...
+ * GROUP BY l_orderkey (TPC-H Q18, Q3), COUNT(*) GROUP BY o_custkey (Q13), SUM(revenue) GROUP BY l_suppkey (Q15), MIN(ps_supplycost)
+ * GROUP BY ps_partkey (Q2): the grouped aggregate fl_<ty>_unfor_aggregate_by computes for a u8 key, for a key of the value column's own
+ * type, with neither column materialised.  The value column and the key column have the SAME element type T and the same n_blocks (FoR
+ * packing makes a narrow column cost its width, not its type: a u8-sized quantity next to a u32 key is a u32 column of width <= 8).
+ * Defined as the composition (all key arithmetic mod 2^T)
+ *     for every block b, every i in 0..1023 with bit i of block b of `mask` set (mask == NULL: every i):
+ *         val = unfor_pack::<W_b >(value block b, references[b*reference_stride])[i]        zero-extended to uint64  (ffor.rs:38-50)
+ *         key = unfor_pack::<KW_b>(key block b, key_references[b*key_reference_stride])[i]
+ *         j   = (key - key_lo) mod 2^T
+ *         if j < n_groups:  counts[j] += 1;  sums[j] += val (mod 2^64);  mins[j] = min(mins[j], val);  maxs[j] = max(maxs[j], val);
+ *                           inside += 1
+ *         else:             outside += 1
+ *     stats[0] += inside;  stats[1] += outside                              -- stats: DEVICE uint64[2], may be NULL
+ * counts, sums, mins and maxs are DEVICE uint64[n_groups] each, 0 <= n_groups <= min(2^T, 2^32); the window [key_lo, key_lo + n_groups
+ * - 1] is cyclic, as fl_<ty>_unfor_set_build's.  THE CALL ACCUMULATES, IT NEVER CLEARS: the caller writes the identities 0 / 0 /
+ * UINT64_MAX / 0 into the arrays, or passes the arrays of an earlier call -- several masks, several columns or several shards of one
+ * table are several calls into one table.  An array passed as NULL is not maintained; when sums, mins and maxs are all NULL no packed
+ * byte of the value column is read (its per-block checks still run); all four NULL is allowed, only stats is counted then.  n_groups
+ * == 0 reads no packed byte, touches no array (they are not checked either) and counts every kept row as outside.  Integer add, min
+ * and max commute: the result is bitwise reproducible.
+ * `mask` has the layout of fl_<ty>_unpack_compare, 32 words per block.  A block whose mask is empty and a block whose key reference
+ * and key width put all its keys outside the window are answered without reading either column; a key block of width 0 inside the
+ * window folds the value block's aggregate into one slot without reading a key byte.  A window of at most 256 groups is aggregated in
+ * a private table per wavefront and added to the arrays once per wavefront; a larger one takes one device atomic per kept element
+ * inside the window and maintained array.  The mixed-width form runs the per-block device checks of fl_<ty>_unfor_compare_widths on
+ * BOTH columns: a failing block is skipped, its FL_DEVERR_* bits are ORed into *err_flag, neither column is read and it contributes
+ * nothing to the arrays or to stats.  The call is asynchronous on `stream`, allocates nothing and uses no scratch memory.
+ * width or key_width > T is FL_ERR_WIDTH (also for an empty column); n_groups above min(2^T, 2^32) FL_ERR_INDEX; n_blocks == 0 FL_OK
+ * (nothing is touched); any required column pointer NULL FL_ERR_NULL (`in` / `packed` / `keys` may be NULL only when no byte of it can
+ * be read: width 0, or its packed bytes == 0); the packed columns, `mask`, the four arrays and `stats` are 16-byte aligned
+ * (FL_ERR_ALIGN).
+ * Out of scope: a value type different from the key type; sparse or hashed keys (a window is dense); windows above 2^32 groups; Delta
+ * columns; the host tier; several value columns or an a o b expression per launch; a larger or workgroup-shared LDS table for mid-size
+ * windows; combining a wavefront's equal keys before the atomic.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_AGGREGATE_BY_WINDOW(T, S)                                                              \
+    int fl_##S##_unfor_aggregate_by_window(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                           unsigned key_width, const T *keys, const T *key_references,    \
+                                           size_t key_reference_stride, const uint32_t *mask /* NULL: every row */, \
+                                           size_t n_blocks, T key_lo, uint64_t n_groups,                  \
+                                           uint64_t *counts /* may be NULL */, uint64_t *sums /* may be NULL */, \
+                                           uint64_t *mins /* may be NULL */, uint64_t *maxs /* may be NULL */, \
+                                           uint64_t *stats /* may be NULL */, void *stream);              \
+    int fl_##S##_unfor_aggregate_by_window_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                                  size_t packed_bytes, const T *references, size_t reference_stride, \
+                                                  const uint8_t *key_widths, const uint64_t *key_offsets, \
+                                                  const T *keys, size_t keys_bytes,                       \
+                                                  const T *key_references, size_t key_reference_stride,   \
+                                                  const uint32_t *mask /* NULL: every row */, size_t n_blocks, \
+                                                  T key_lo, uint64_t n_groups,                            \
+                                                  uint64_t *counts /* may be NULL */, uint64_t *sums /* may be NULL */, \
+                                                  uint64_t *mins /* may be NULL */, uint64_t *maxs /* may be NULL */, \
+                                                  uint64_t *stats /* may be NULL */, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_AGGREGATE_BY_WINDOW(uint8_t, u8)
+FL_DECLARE_AGGREGATE_BY_WINDOW(uint16_t, u16)
+FL_DECLARE_AGGREGATE_BY_WINDOW(uint32_t, u32)
+FL_DECLARE_AGGREGATE_BY_WINDOW(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_compare_in_widths = fl_##S##_unfor_compare_in_widths;            \
         static constexpr auto unfor_set_build = fl_##S##_unfor_set_build;                            \
         static constexpr auto unfor_set_build_widths = fl_##S##_unfor_set_build_widths;              \
+        static constexpr auto unfor_aggregate_by_window = fl_##S##_unfor_aggregate_by_window;        \
+        static constexpr auto unfor_aggregate_by_window_widths = fl_##S##_unfor_aggregate_by_window_widths; \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -228,6 +230,15 @@ template <typename T> struct FoR : BitPacking<T> {
                                        std::size_t n_blocks, T set_lo, std::uint64_t set_bits, std::uint32_t* d_set_words,
                                        std::uint64_t* d_stats = nullptr, void* stream = nullptr)
     { detail::check(A::unfor_set_build((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, set_lo, set_bits, d_set_words, d_stats, stream), "unfor_set_build_device"); }
+    // GROUP BY a key column of the same type inside the window [key_lo, key_lo + n_groups - 1]: every row d_mask keeps (nullptr: every
+    // row) whose key k has j = (k - key_lo) mod 2^T < n_groups updates d_counts[j] / d_sums[j] / d_mins[j] / d_maxs[j] (uint64[n_groups]
+    // each; nullptr: not maintained) with its value; d_stats (nullptr: not counted) += {kept rows inside the window, kept rows outside}.
+    // Accumulates, never clears: write the identities 0 / 0 / UINT64_MAX / 0 first, or pass an earlier call's arrays
+    static void unfor_aggregate_by_window_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, std::size_t key_width,
+                                                 const T* d_keys, const T* d_key_refs, std::size_t key_ref_stride, const std::uint32_t* d_mask,
+                                                 std::size_t n_blocks, T key_lo, std::uint64_t n_groups, std::uint64_t* d_counts, std::uint64_t* d_sums,
+                                                 std::uint64_t* d_mins, std::uint64_t* d_maxs, std::uint64_t* d_stats = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_aggregate_by_window((unsigned)width, d_packed, d_refs, ref_stride, (unsigned)key_width, d_keys, d_key_refs, key_ref_stride, d_mask, n_blocks, key_lo, n_groups, d_counts, d_sums, d_mins, d_maxs, d_stats, stream), "unfor_aggregate_by_window_device"); }
     // a <op> b between two FoR-packed columns of T with the same block count (signed: of the two's-complement values), joined with the
     // mask so far as unfor_compare_range_device does; a block pair the references and widths decide reads neither column
     static void unfor_compare_columns_device(std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride, std::size_t width_b,
@@ -516,6 +527,18 @@ inline void unfor_set_build_widths_device(const std::uint8_t* d_widths, const st
                                           T set_lo, std::uint64_t set_bits, std::uint32_t* d_set_words, std::uint64_t* d_stats = nullptr,
                                           std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_set_build_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, set_lo, set_bits, d_set_words, d_stats, d_err_flag, stream), "unfor_set_build_widths"); }
+// ... and the grouped aggregate of a mixed-width value column by a mixed-width key column of the same type inside a dense window of the
+// key domain: d_counts / d_sums / d_mins / d_maxs[(key - key_lo) mod 2^T] are updated for every kept row inside the window (nullptr: not
+// maintained), d_stats += {inside, outside}; never clears
+template <typename T>
+inline void unfor_aggregate_by_window_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                                    const T* d_references, std::size_t reference_stride, const std::uint8_t* d_key_widths,
+                                                    const std::uint64_t* d_key_offsets, const T* d_keys, std::size_t keys_bytes, const T* d_key_references,
+                                                    std::size_t key_reference_stride, const std::uint32_t* d_mask, std::size_t n_blocks, T key_lo,
+                                                    std::uint64_t n_groups, std::uint64_t* d_counts, std::uint64_t* d_sums, std::uint64_t* d_mins,
+                                                    std::uint64_t* d_maxs, std::uint64_t* d_stats = nullptr, std::uint32_t* d_err_flag = nullptr,
+                                                    void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_aggregate_by_window_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_key_widths, d_key_offsets, d_keys, keys_bytes, d_key_references, key_reference_stride, d_mask, n_blocks, key_lo, n_groups, d_counts, d_sums, d_mins, d_maxs, d_stats, d_err_flag, stream), "unfor_aggregate_by_window_widths"); }
 // ... and a predicate between two mixed-width columns of T with the same block count, a <op> b (signed: of the two's-complement values),
 // chained the same way; both columns get unfor_pack_widths' device checks, a block that fails either keeps its mask words
 template <typename T>
