@@ -23,6 +23,7 @@ _I = ctypes.c_int
 _U32 = ctypes.c_uint32
 _S = ctypes.c_char_p
 _T = "T"                                # the element type of a per-type row: CTYPE[ty]
+_U8 = ctypes.c_uint8
 
 
 def _ptr(*types):
@@ -149,6 +150,15 @@ _SIGNATURES = (
     ("AGGREGATE_BY_WINDOW", "fl_{vty}_unfor_aggregate_by_window", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
     ("AGGREGATE_BY_WINDOW", "fl_{vty}_unfor_aggregate_by_window_widths", _I,
      [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P, _P]),
+    # FL_DECLARE_LOOKUP (device tier): table[(key - key_lo) mod 2^T] of the rows a mask keeps, the payload of the key's own type, written
+    # in full-width packed order -- the probe side of a payload join ({vty} as above: these rows' refusals are pinned by
+    # tests/test_lookup_cpu.py)
+    ("LOOKUP", "fl_{vty}_unfor_lookup", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _T, _P, _P, _P, _P]),
+    ("LOOKUP", "fl_{vty}_unfor_lookup_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _T, _P, _P, _P, _P, _P]),
+    # FL_DECLARE_LOOKUP_U8 (device tier): the same with a uint8_t payload (for u8 keys the pair above under a second name: every
+    # element type has one surface)
+    ("LOOKUP_U8", "fl_{vty}_unfor_lookup_u8", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _U8, _P, _P, _P, _P]),
+    ("LOOKUP_U8", "fl_{vty}_unfor_lookup_u8_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _U8, _P, _P, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -234,6 +244,12 @@ def set_build_symbols():
 def aggregate_by_window_symbols():
     """The symbols FL_DECLARE_AGGREGATE_BY_WINDOW declares: for all four element types the two windowed group-by entry points."""
     return _symbols("AGGREGATE_BY_WINDOW")
+
+
+def lookup_symbols():
+    """The symbols FL_DECLARE_LOOKUP and FL_DECLARE_LOOKUP_U8 declare: for all four key types the two lookups with a payload of the
+    key's own type and the two with a uint8_t payload (for u8 keys the same two functions under a second name)."""
+    return _symbols("LOOKUP", "LOOKUP_U8")
 
 
 _LIB = None

@@ -513,6 +513,25 @@ class FoR:
         return ms, stats
 
     @staticmethod
+    def unfor_lookup(width, packed, reference, lo, table, present=None, missing=0, mask=None, hit=None, output=None, stats=None, n_blocks=None):
+        """The probe side of a payload join (unfor_lookup_widths' uniform form): for every row `mask` keeps (None: every row) with the
+        key k = FoR.unfor_pack(width, block b, reference)[i] and j = (k - lo) mod 2^T, table[j] when j < len(table) and bit j of
+        `present` (a MemberSet with the window lo, len(table); None: every slot) is set, `missing` otherwise.  `table`: a CUDA tensor
+        of the key's own type or of uint8.  Returns (column, hit, stats) as unfor_lookup_widths does: the column in full-width packed
+        order (fl.full_width_column), the hits as a mask (`hit=mask`: in place), stats += (hits, kept rows that miss).  Device tier
+        only.  n_blocks is only needed for width == 0 without a mask, a hit or an output."""
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("unfor_lookup is device tier (pass CUDA tensors)")
+        n = _uniform_blocks(src, width, "unfor_lookup", n_blocks, (mask if _is_torch(mask) else None, 32), (hit if _is_torch(hit) else None, 32),
+                            (output, 1024))
+        suffix, args, result = _lookup_args(src, n, lo, table, present, missing, mask, hit, output, stats)
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        _launch(f"fl_{ty}_unfor_lookup{suffix}", src.x.device, width, src.ptr, aux.ptr, stride, *args)
+        return result
+
+    @staticmethod
     def unfor_aggregate_by_window(width, packed, reference, key_width, key_packed, key_reference, lo, n_groups, mask=None,
                                   what=("count", "sum"), into=None, n_blocks=None):
         """GROUP BY a key column of the value column's own type inside a dense window of the key domain: every row `mask` keeps (a
@@ -1245,6 +1264,84 @@ def unfor_set_build_widths(widths, offsets, packed, references, lo, bits, mask=N
             ms.words.data_ptr() if ms.bits else None, stats.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_unfor_set_build_widths")        # bitpacking.rs:93,126 unreachable!(); :111-113
     return ms, stats
+
+
+def full_width_column(ty, n_blocks, device):
+    """(widths, offsets, references) of a column of `n_blocks` FULL-WIDTH blocks of `ty` on `device`: every width T, block b at byte
+    b * 128 * T, one zero reference broadcast to every block.  A full-width bit-packed block is a pure permutation of its 1024 values
+    (for u8: the identity), which is the order unfor_lookup* writes -- so with these three a lookup's output drops into any `_widths`
+    operator as its packed column: a u8 result as the key column of unfor_aggregate_by_widths, a result of the key's own type as the
+    key column of a second lookup."""
+    import torch
+    if ty not in _lib.BITS:
+        raise ValueError(f"ty must be one of {list(_lib.TYPES)}")
+    T = _lib.BITS[ty]
+    widths = torch.full((int(n_blocks),), T, dtype=torch.uint8, device=device)
+    offsets = torch.arange(int(n_blocks), dtype=torch.int64, device=device) * (128 * T)
+    references = torch.zeros(1, dtype={"u8": torch.uint8, "u16": torch.uint16, "u32": torch.uint32, "u64": torch.uint64}[ty], device=device)
+    return widths, offsets, references
+
+
+def _lookup_args(src, n, lo, table, present, missing, mask, hit, output, stats):
+    """What both lookup forms share behind the column: the entry's name suffix, the C arguments from `mask` to `stats`, and the three
+    tensors the call returns.  `table.dtype` picks the entry: the key's own element size (payload U = T), or one byte (uint8)."""
+    import torch
+    ty = src.ty
+    T = _lib.BITS[ty]
+    tb = _Arg(table)
+    _same_tier(src, tb)
+    if tb.x.dtype.is_floating_point or tb.x.element_size() not in (1, T // 8):
+        raise TypeError(f"table must be a {ty} or a uint8 tensor, got {tb.x.dtype}")
+    uty = _NP[tb.x.element_size()]
+    U = _lib.BITS[uty]
+    lo, n_slots = int(lo) & ((1 << T) - 1), tb.n
+    if n_slots > min(1 << T, 1 << 32) or n_slots * (U // 8) >= 1 << 31:
+        raise ValueError(f"table holds {n_slots} slots of {U // 8} bytes: at most {min(1 << T, 1 << 32)} slots and fewer than 2^31 bytes")
+    pr = None
+    if present is not None:
+        if not isinstance(present, MemberSet):
+            raise TypeError("present must be a MemberSet (member_set, or an unfor_set_build result)")
+        if present.ty != ty:
+            raise TypeError(f"present is a member set of {present.ty}, the key column of {ty}")
+        if (int(present.lo) & ((1 << T) - 1), present.bits) != (lo, n_slots):
+            raise ValueError(f"present has the window (lo={present.lo}, bits={present.bits}), the table (lo={lo}, slots={n_slots})")
+        pr = present.on(src.x.device) if n_slots else None
+    m = _select_mask(src, mask, n) if mask is not None else None
+    out = _out(tb, output, uty, n * 1024, "unfor_lookup")
+    _same_tier(src, out)
+    h = _consumer_out(src, hit, torch.int32, n * 32, "unfor_lookup hit")
+    if stats is None:
+        stats = torch.zeros(2, dtype=torch.int64, device=src.x.device)
+    st = _block_words(stats, "stats", 2, 8, src, 1)[0]
+    args = (m.ptr if m is not None and n else None, n, _scalar(ty, lo), n_slots, tb.ptr if n_slots else None,
+            pr.data_ptr() if pr is not None else None, _scalar(uty, missing), out.ptr if n else None, h.data_ptr() if n else None, st.ptr)
+    return ("" if U == T else "_u8"), args, (out.x, h, st.x)
+
+
+def unfor_lookup_widths(widths, offsets, packed, references, lo, table, present=None, missing=0, mask=None, hit=None, output=None, stats=None,
+                        check=True):
+    """The probe side of a payload join over a mixed-width key column: for every row `mask` keeps (32 words per block,
+    unfor_compare_widths' layout; None: every row) with the key k = unfor_pack_widths(widths, offsets, packed, references)[row] and
+    j = (k - lo) mod 2^T, the result is table[j] when j < len(table) and bit j of `present` is set (a MemberSet with the window lo,
+    len(table) -- ValueError otherwise; None: every slot is present), `missing` otherwise.  `table` is a CUDA tensor of the key's own
+    type or of uint8; its dtype picks the entry point and is the result's.  Returns (column, hit, stats):
+      * column: n_blocks * 1024 values, every block in FULL-WIDTH PACKED order -- with fl.full_width_column(ty of the table, ...) the
+        packed column of any `_widths` operator (a uint8 column is in row order: the u8 key column of unfor_aggregate_by_widths as it
+        stands; BitPacking.unpack(T, column) gives any other back in row order); `output` if given;
+      * hit: the hits as a mask of 32 words per block; `hit` if given, and `hit=mask` is the in-place form;
+      * stats: a CUDA int64[2] tensor holding uint64 bits, += (hits, kept rows that miss); `stats` if given, else a fresh zeroed one.
+    A block whose mask is empty and a block outside the window are all `missing` without a packed load or a gather; a width-0 block
+    inside the window takes one table read.  A table of at most 8192 bytes is looked up in LDS, a larger one gathered from device
+    memory.  The per-block device checks of unfor_compare_widths: a block that fails them is left untouched (column, hit and stats);
+    `check=True` reads the device error flag back (one sync) and raises, `check=False` stays asynchronous."""
+    src = _Arg(packed)
+    ty = src.ty
+    n, lead = _widths_column("unfor_lookup_widths", src, widths, offsets, references=references)
+    suffix, args, result = _lookup_args(src, n, lo, table, present, missing, mask, hit, output, stats)
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_lookup{suffix}_widths", src.x.device, *lead, *args, flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_lookup{suffix}_widths")   # bitpacking.rs:93,126 unreachable!(); :111-113
+    return result
 
 
 class GroupTable:

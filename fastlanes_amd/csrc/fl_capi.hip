@@ -21,6 +21,7 @@
 #include "fl_for_compare_in.hpp"
 #include "fl_aggregate_by_columns.hpp"
 #include "fl_set_build.hpp"
+#include "fl_lookup.hpp"
 #include "fl_aggregate_by_window.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
@@ -596,6 +597,71 @@ int run_unfor_aggregate_by_window(const Column& col, const T* packed, const T* r
     const AggregateByWindowArgs a =
         aggregate_by_window_args<T>(col, packed, refs, ref_stride, kcol, keys, key_refs, key_ref_stride, mask, n_blocks, key_lo, n_groups, t, err_flag, sh);
     const aggregate_by_window_launch_t fn = aggregate_by_window_launcher<T>(aggregate_by_window_lds_tier(n_groups) ? AGGW_LDS : AGGW_MEM);
+    if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
+    return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// unfor_lookup (fl_lookup.hpp): table[(key - key_lo) mod 2^T] of every kept row of a key column, U = T or uint8_t, written in full-width
+// packed order with the hits as a mask beside it.  One validator, one builder.  The validator's order is run_unfor_set_build's: the
+// width; n_slots (FL_ERR_INDEX: above min(2^T, 2^32) slots, or a table of 2^31 bytes or more); the empty column; `table` (never read
+// when n_slots == 0), `out` and the column's pointers (FL_ERR_NULL; `mask`, `present`, `hit_mask` and `stats` may be NULL); alignment.
+// An empty window reads neither the table nor the bitmap: the validator drops them, so they are neither read nor checked.  n_slots
+// decides the tier here, once per call (fl_lookup_map.hpp: lookup_tier).  The persistent grid takes the policy's waves and blocks per
+// wavefront as run_unfor_set_build does.
+struct LookupTable {
+    const void* table;
+    const uint32_t* present;
+    uint64_t missing;
+    void* out;
+    uint32_t* hit_mask;
+    uint64_t* stats;
+};
+template <typename T>
+int lookup_refusal(const Column& col, const T*& packed, const T* refs, const uint32_t* mask, size_t n_blocks, uint64_t n_slots, unsigned payload_bytes,
+                   LookupTable& t)
+{
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
+    if (lookup_slots_refused(Elem<T>::BITS, n_slots, payload_bytes)) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (n_slots == 0) t.table = t.present = nullptr;                      // the empty window: never read, never checked
+    else if (!t.table) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, refs) || !t.out) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(mask) || misaligned(t.hit_mask) || misaligned(t.present) || misaligned(t.table) || misaligned(t.out) ||
+        misaligned(t.stats))
+        return FL_ERR_ALIGN;
+    return FL_OK;
+}
+template <typename T>
+LookupArgs lookup_args(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
+                       uint64_t n_slots, unsigned payload_bytes, const LookupTable& t, uint32_t* err_flag, const WaveShape& sh)
+{
+    const ForPredicate p = set_window(Elem<T>::BITS, key_lo, n_slots);
+    LookupArgs a;
+    widths_args<T>(a.col, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    a.refs = refs;
+    a.mask = mask;
+    a.table = t.table;
+    a.present = t.present;
+    a.out = static_cast<char*>(t.out);
+    a.hit_mask = t.hit_mask;
+    a.stats = t.stats;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.missing = t.missing;
+    a.cmp_none = p.none ? 1u : 0u;
+    a.table_bytes = (unsigned)(n_slots * payload_bytes);
+    a.present_bytes = t.present ? (unsigned)(4u * set_word_count(n_slots)) : 0u;
+    a.run = 0;
+    return a;
+}
+template <typename T>
+int run_unfor_lookup(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
+                     uint64_t n_slots, unsigned payload_bytes, LookupTable t, uint32_t* err_flag, void* stream)
+{
+    if (const int rc = lookup_refusal<T>(col, packed, refs, mask, n_blocks, n_slots, payload_bytes, t); rc != FL_OK || n_blocks == 0) return rc;
+    const WaveShape sh = with_policy({0, 0u, 0u});
+    const LookupArgs a = lookup_args<T>(col, packed, refs, ref_stride, mask, n_blocks, key_lo, n_slots, payload_bytes, t, err_flag, sh);
+    const lookup_launch_t fn = lookup_launcher<T>(payload_bytes, lookup_tier(n_slots, payload_bytes));
     if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
     return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
@@ -1209,6 +1275,32 @@ FL_DEFINE_AGGREGATE_BY_WINDOW(uint8_t, u8)
 FL_DEFINE_AGGREGATE_BY_WINDOW(uint16_t, u16)
 FL_DEFINE_AGGREGATE_BY_WINDOW(uint32_t, u32)
 FL_DEFINE_AGGREGATE_BY_WINDOW(uint64_t, u64)
+
+#define FL_DEFINE_LOOKUP_FORMS(T, S, U, NAME)                                                              \
+    int fl_##S##_##NAME(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, T lo, uint64_t ns, const U* tb, \
+                        const uint32_t* pr, U ms, U* out, uint32_t* hm, uint64_t* st, void* s)            \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, in, r, mask, tb, pr, out, hm, st);                                              \
+        return run_unfor_lookup<T>({false, w}, in, r, rs, mask, n, lo, ns, (unsigned)sizeof(U), {tb, pr, ms, out, hm, st}, nullptr, s); \
+    }                                                                                                     \
+    int fl_##S##_##NAME##_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
+                                 size_t n, T lo, uint64_t ns, const U* tb, const uint32_t* pr, U ms, U* out, uint32_t* hm, uint64_t* st, \
+                                 uint32_t* ef, void* s)                                                   \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, w, o, pk, r, mask, tb, pr, out, hm, st, ef);                                    \
+        return run_unfor_lookup<T>({true, 0, w, o, pb}, pk, r, rs, mask, n, lo, ns, (unsigned)sizeof(U), {tb, pr, ms, out, hm, st}, ef, s); \
+    }
+#define FL_DEFINE_LOOKUP(T, S) FL_DEFINE_LOOKUP_FORMS(T, S, T, unfor_lookup)
+#define FL_DEFINE_LOOKUP_U8(T, S) FL_DEFINE_LOOKUP_FORMS(T, S, uint8_t, unfor_lookup_u8)
+
+FL_DEFINE_LOOKUP(uint8_t, u8)
+FL_DEFINE_LOOKUP(uint16_t, u16)
+FL_DEFINE_LOOKUP(uint32_t, u32)
+FL_DEFINE_LOOKUP(uint64_t, u64)
+FL_DEFINE_LOOKUP_U8(uint8_t, u8)
+FL_DEFINE_LOOKUP_U8(uint16_t, u16)
+FL_DEFINE_LOOKUP_U8(uint32_t, u32)
+FL_DEFINE_LOOKUP_U8(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                               \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \

@@ -17,6 +17,7 @@
 //   21 unfor_aggregate_by_columns (count / sum / min / max per u8 key of a * b, a + b or a - b between two such columns under a mask, all three columns FoR-packed; fl_aggregate_by_columns.hpp)
 //   22 unfor_set_build (the member set of the values a mask keeps of such a column, ORed into a window's bitmap: the build side of unfor_compare_in; fl_set_build.hpp)
 //   23 unfor_aggregate_by_window (count / sum / min / max per key of a dense window of the key domain, value and key column FoR-packed and of one type, accumulated into the caller's arrays; fl_aggregate_by_window.hpp)
+//   24 unfor_lookup (a dimension attribute of the key's own type or u8 fetched through such a column inside a dense window of the key domain under a mask, written in full-width packed order: the probe side of a payload join; fl_lookup.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -34,6 +35,7 @@
 #include "fl_aggregate_by_columns.hpp"
 #include "fl_set_build.hpp"
 #include "fl_aggregate_by_window.hpp"
+#include "fl_lookup.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -177,7 +179,21 @@ template <> aggregate_by_window_launch_t aggregate_by_window_launcher<T>(int tie
     }
     return tier == AGGW_LDS ? &launch_aggregate_by_window<T, AGGW_LDS> : nullptr;
 }
+#elif FL_FAMILY == 24
+template <> lookup_launch_t lookup_launcher<T>(unsigned payload_bytes, int tier)
+{
+    if (payload_bytes == sizeof(T)) {
+        if constexpr (sizeof(T) >= 2) {                     // a table above LOOKUP_LDS_BYTES: 256 slots of u8 never are
+            if (tier == LOOKUP_MEM) return &launch_lookup<T, T, LOOKUP_MEM>;
+        }
+        return tier == LOOKUP_LDS ? &launch_lookup<T, T, LOOKUP_LDS> : nullptr;
+    }
+    if constexpr (sizeof(T) >= 2) {                         // the u8 payload of a wider key (u8's own is the pair above)
+        if (payload_bytes == 1u) return tier == LOOKUP_LDS ? &launch_lookup<T, uint8_t, LOOKUP_LDS> : tier == LOOKUP_MEM ? &launch_lookup<T, uint8_t, LOOKUP_MEM> : nullptr;
+    }
+    return nullptr;
+}
 #else
-#error "FL_FAMILY must be 0..6 or 8..23"
+#error "FL_FAMILY must be 0..6 or 8..24"
 #endif
 }  // namespace fl

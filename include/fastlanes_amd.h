@@ -876,6 +876,89 @@ FL_DECLARE_AGGREGATE_BY_WINDOW(uint16_t, u16)
 FL_DECLARE_AGGREGATE_BY_WINDOW(uint32_t, u32)
 FL_DECLARE_AGGREGATE_BY_WINDOW(uint64_t, u64)
 
+/*
+ * EXTENSION: LOOK UP A DIMENSION ATTRIBUTE through a packed key -- the probe side of a join that carries a payload:
+ * SUM(revenue) GROUP BY n_name reached through l_suppkey or o_custkey (TPC-H Q5, Q7, Q8, Q10), GROUP BY d_year, p_brand through
+ * lo_orderdate and lo_partkey (Star Schema Benchmark Q2 on), o_custkey through l_orderkey, ps_supplycost in Q9.  The window is the dense
+ * one fl_<ty>_unfor_set_build, fl_<ty>_unfor_compare_in and fl_<ty>_unfor_aggregate_by_window share; the result is written AS A COLUMN
+ * EVERY OPERATOR HERE CONSUMES UNCHANGED.  The payload type U is the key's own type T (fl_<ty>_unfor_lookup) or uint8_t
+ * (fl_<ty>_unfor_lookup_u8; every element type has the same surface, so u8 declares it too: there it IS fl_u8_unfor_lookup, the
+ * same kernel under its second name).  Defined as the composition (all key arithmetic mod 2^T)
+ *     for every block b, every i in 0..1023:
+ *         kept = mask == NULL or bit i of block b of `mask`
+ *         key  = unfor_pack::<W_b>(key block b, references[b*reference_stride])[i]                                (ffor.rs:38-50)
+ *         j    = (key - key_lo) mod 2^T
+ *         hit  = kept and j < n_slots and (present == NULL or bit j of present)
+ *         v[i] = hit ? table[j] : missing;   h[i] = hit
+ *     out block b      = pack::<8*sizeof(U)>(v)          -- a permutation of v (bitpacking.rs); for U = uint8_t it is v itself
+ *     hit_mask block b = h                               -- 32 words, the layout of fl_<ty>_unpack_compare; may be NULL
+ *     stats[0] += #hit;  stats[1] += #(kept and not hit) -- stats: DEVICE uint64[2], may be NULL; it accumulates, as everywhere else
+ * `table` is DEVICE U[n_slots], 0 <= n_slots <= min(2^T, 2^32); `present` has the layout of fl_<ty>_unfor_compare_in's set_words with
+ * set_lo = key_lo and set_bits = n_slots (bits past n_slots are ignored) and may be NULL: every slot is present.  `out` is DEVICE
+ * U[n_blocks * 1024].  A full-width bit-packed block is a pure permutation of its 1024 values, so
+ *   - a uint8_t result is, as it stands, the FoR-packed u8 key column of fl_<ty>_unfor_aggregate_by and ..._by_columns (key_width = 8,
+ *     one zero reference, stride 0);
+ *   - a result of the key's own type is a valid input of every fl_<ty>_unfor_* entry point at width T with a zero reference -- a second
+ *     lookup among them (l_orderkey -> o_custkey -> c_nationkey); fl_<ty>_unpack at width T gives it back in row order.
+ * Every valid block's whole output block is always written, and its 128 mask bytes whenever hit_mask != NULL; `hit_mask` may be `mask`
+ * itself (a block's incoming mask is read before its words are written).  n_slots == 0 reads no packed byte and no table byte, writes
+ * `missing` everywhere and counts every kept row as a miss.
+ * A block whose mask is empty and a block whose reference and width put all its keys outside the window are all `missing` without a
+ * packed load or a gather; a width-0 block inside the window takes one table read.  A table of at most 8192 bytes is copied into LDS
+ * once per wavefront; a larger one is gathered from device memory through one bounded buffer descriptor (default cache policy).  The
+ * mixed-width form runs the per-block device checks of fl_<ty>_unfor_compare_widths: a failing block is skipped, its FL_DEVERR_* bit is
+ * ORed into *err_flag, its `out` block and mask words are left untouched and it adds nothing to stats.  The call is asynchronous on
+ * `stream`, allocates nothing and uses no scratch memory.
+ * width > T is FL_ERR_WIDTH (also for an empty column); n_slots above min(2^T, 2^32), or n_slots * sizeof(U) >= 2^31, FL_ERR_INDEX;
+ * n_blocks == 0 FL_OK (nothing is touched); table == NULL with n_slots > 0, out == NULL or any required column pointer NULL FL_ERR_NULL
+ * (`in` / `packed` may be NULL only when no byte of it can be read: width 0, or packed_bytes == 0); the packed column, `mask`,
+ * `hit_mask`, `present`, `table`, `out` and `stats` are 16-byte aligned (FL_ERR_ALIGN).
+ * Out of scope: payload types other than T and uint8_t; several tables per launch; sparse or hashed keys (a window is dense); Delta
+ * columns; the host tier; tables of 2^31 bytes or more; a fused GROUP BY-through-lookup kernel (lookup -> fl_<ty>_unfor_aggregate_by
+ * serves it; whether fusing pays is a later change's question).
+ * (Declared by two macros of their own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol
+ * lists are pinned surfaces.)
+ */
+#define FL_DECLARE_LOOKUP(T, S)                                                                           \
+    int fl_##S##_unfor_lookup(unsigned width, const T *in, const T *references, size_t reference_stride,  \
+                              const uint32_t *mask /* NULL: every row */, size_t n_blocks,                \
+                              T key_lo, uint64_t n_slots, const T *table /* NULL with n_slots 0 */,       \
+                              const uint32_t *present /* may be NULL */, T missing, T *out,               \
+                              uint32_t *hit_mask /* may be NULL, may be mask */,                          \
+                              uint64_t *stats /* may be NULL */, void *stream);                           \
+    int fl_##S##_unfor_lookup_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,     \
+                                     size_t packed_bytes, const T *references, size_t reference_stride,   \
+                                     const uint32_t *mask /* NULL: every row */, size_t n_blocks,         \
+                                     T key_lo, uint64_t n_slots, const T *table /* NULL with n_slots 0 */, \
+                                     const uint32_t *present /* may be NULL */, T missing, T *out,        \
+                                     uint32_t *hit_mask /* may be NULL, may be mask */,                   \
+                                     uint64_t *stats /* may be NULL */, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_LOOKUP(uint8_t, u8)
+FL_DECLARE_LOOKUP(uint16_t, u16)
+FL_DECLARE_LOOKUP(uint32_t, u32)
+FL_DECLARE_LOOKUP(uint64_t, u64)
+
+#define FL_DECLARE_LOOKUP_U8(T, S)                                                                        \
+    int fl_##S##_unfor_lookup_u8(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                 const uint32_t *mask /* NULL: every row */, size_t n_blocks,             \
+                                 T key_lo, uint64_t n_slots, const uint8_t *table /* NULL with n_slots 0 */, \
+                                 const uint32_t *present /* may be NULL */, uint8_t missing, uint8_t *out, \
+                                 uint32_t *hit_mask /* may be NULL, may be mask */,                       \
+                                 uint64_t *stats /* may be NULL */, void *stream);                        \
+    int fl_##S##_unfor_lookup_u8_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,  \
+                                        size_t packed_bytes, const T *references, size_t reference_stride, \
+                                        const uint32_t *mask /* NULL: every row */, size_t n_blocks,      \
+                                        T key_lo, uint64_t n_slots, const uint8_t *table /* NULL with n_slots 0 */, \
+                                        const uint32_t *present /* may be NULL */, uint8_t missing, uint8_t *out, \
+                                        uint32_t *hit_mask /* may be NULL, may be mask */,                \
+                                        uint64_t *stats /* may be NULL */, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_LOOKUP_U8(uint8_t, u8)
+FL_DECLARE_LOOKUP_U8(uint16_t, u16)
+FL_DECLARE_LOOKUP_U8(uint32_t, u32)
+FL_DECLARE_LOOKUP_U8(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,10 @@ template <typename T> struct Abi;
         static constexpr auto unfor_set_build_widths = fl_##S##_unfor_set_build_widths;              \
         static constexpr auto unfor_aggregate_by_window = fl_##S##_unfor_aggregate_by_window;        \
         static constexpr auto unfor_aggregate_by_window_widths = fl_##S##_unfor_aggregate_by_window_widths; \
+        static constexpr auto unfor_lookup = fl_##S##_unfor_lookup;                                  \
+        static constexpr auto unfor_lookup_widths = fl_##S##_unfor_lookup_widths;                    \
+        static constexpr auto unfor_lookup_u8 = fl_##S##_unfor_lookup_u8;                            \
+        static constexpr auto unfor_lookup_u8_widths = fl_##S##_unfor_lookup_u8_widths;              \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -239,6 +243,21 @@ template <typename T> struct FoR : BitPacking<T> {
                                                  std::size_t n_blocks, T key_lo, std::uint64_t n_groups, std::uint64_t* d_counts, std::uint64_t* d_sums,
                                                  std::uint64_t* d_mins, std::uint64_t* d_maxs, std::uint64_t* d_stats = nullptr, void* stream = nullptr)
     { detail::check(A::unfor_aggregate_by_window((unsigned)width, d_packed, d_refs, ref_stride, (unsigned)key_width, d_keys, d_key_refs, key_ref_stride, d_mask, n_blocks, key_lo, n_groups, d_counts, d_sums, d_mins, d_maxs, d_stats, stream), "unfor_aggregate_by_window_device"); }
+    // the probe side of a payload join: d_out block b = pack::<T bits>(v), v[i] = d_table[j] for a row d_mask keeps (nullptr: every row)
+    // whose key k has j = (k - key_lo) mod 2^T < n_slots and bit j of d_present set (nullptr: every slot), `missing` otherwise; d_hit_mask
+    // (nullptr: not written; may be d_mask) = the hits, d_stats (nullptr: not counted) += {hits, kept rows that miss}.  d_out is a
+    // width-T column with a zero reference: any unfor_* entry point takes it, a second lookup among them
+    static void unfor_lookup_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
+                                    std::size_t n_blocks, T key_lo, std::uint64_t n_slots, const T* d_table, const std::uint32_t* d_present, T missing,
+                                    T* d_out, std::uint32_t* d_hit_mask = nullptr, std::uint64_t* d_stats = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_lookup((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, missing, d_out, d_hit_mask, d_stats, stream), "unfor_lookup_device"); }
+    // ... with a uint8_t payload (for T = u8 the function above): d_out holds the 1024 values of a block in row order -- as it stands the u8 key
+    // column (key_width 8, one zero reference, stride 0) of unfor_aggregate_by_device and unfor_aggregate_by_columns_device
+    static void unfor_lookup_u8_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, const std::uint32_t* d_mask,
+                                       std::size_t n_blocks, T key_lo, std::uint64_t n_slots, const std::uint8_t* d_table,
+                                       const std::uint32_t* d_present, std::uint8_t missing, std::uint8_t* d_out, std::uint32_t* d_hit_mask = nullptr,
+                                       std::uint64_t* d_stats = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_lookup_u8((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, missing, d_out, d_hit_mask, d_stats, stream), "unfor_lookup_u8_device"); }
     // a <op> b between two FoR-packed columns of T with the same block count (signed: of the two's-complement values), joined with the
     // mask so far as unfor_compare_range_device does; a block pair the references and widths decide reads neither column
     static void unfor_compare_columns_device(std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride, std::size_t width_b,
@@ -539,6 +558,24 @@ inline void unfor_aggregate_by_window_widths_device(const std::uint8_t* d_widths
                                                     std::uint64_t* d_maxs, std::uint64_t* d_stats = nullptr, std::uint32_t* d_err_flag = nullptr,
                                                     void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_aggregate_by_window_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_key_widths, d_key_offsets, d_keys, keys_bytes, d_key_references, key_reference_stride, d_mask, n_blocks, key_lo, n_groups, d_counts, d_sums, d_mins, d_maxs, d_stats, d_err_flag, stream), "unfor_aggregate_by_window_widths"); }
+// ... and the payload join's probe side over a mixed-width key column: d_out block b = pack::<T bits>(v), v[i] = d_table[(key - key_lo)
+// mod 2^T] for a kept row inside the window whose d_present bit is set (nullptr: every slot), `missing` otherwise; d_hit_mask (nullptr: not
+// written; may be d_mask) = the hits, d_stats += {hits, kept rows that miss}; a block that fails the device checks is left untouched
+template <typename T>
+inline void unfor_lookup_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                       const T* d_references, std::size_t reference_stride, const std::uint32_t* d_mask, std::size_t n_blocks, T key_lo,
+                                       std::uint64_t n_slots, const T* d_table, const std::uint32_t* d_present, T missing, T* d_out,
+                                       std::uint32_t* d_hit_mask = nullptr, std::uint64_t* d_stats = nullptr, std::uint32_t* d_err_flag = nullptr,
+                                       void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_lookup_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, missing, d_out, d_hit_mask, d_stats, d_err_flag, stream), "unfor_lookup_widths"); }
+// ... with a uint8_t payload (for T = u8 the function above): d_out is the u8 key column of the grouped aggregates as it stands
+template <typename T>
+inline void unfor_lookup_u8_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                          const T* d_references, std::size_t reference_stride, const std::uint32_t* d_mask, std::size_t n_blocks,
+                                          T key_lo, std::uint64_t n_slots, const std::uint8_t* d_table, const std::uint32_t* d_present,
+                                          std::uint8_t missing, std::uint8_t* d_out, std::uint32_t* d_hit_mask = nullptr, std::uint64_t* d_stats = nullptr,
+                                          std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_lookup_u8_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, missing, d_out, d_hit_mask, d_stats, d_err_flag, stream), "unfor_lookup_u8_widths"); }
 // ... and a predicate between two mixed-width columns of T with the same block count, a <op> b (signed: of the two's-complement values),
 // chained the same way; both columns get unfor_pack_widths' device checks, a block that fails either keeps its mask words
 template <typename T>
