@@ -159,6 +159,12 @@ _SIGNATURES = (
     # element type has one surface)
     ("LOOKUP_U8", "fl_{vty}_unfor_lookup_u8", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _U8, _P, _P, _P, _P]),
     ("LOOKUP_U8", "fl_{vty}_unfor_lookup_u8_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _U8, _P, _P, _P, _P, _P]),
+    # FL_DECLARE_AGGREGATE_BY_LOOKUP (device tier): unfor_lookup_u8 and unfor_aggregate_by in one pass -- COUNT / SUM / MIN / MAX per u8
+    # attribute fetched through a key column of the value column's own type, no per-row output ({vty} as above: these rows' refusals
+    # are pinned by tests/test_aggregate_by_lookup_cpu.py)
+    ("AGGREGATE_BY_LOOKUP", "fl_{vty}_unfor_aggregate_by_lookup", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
+    ("AGGREGATE_BY_LOOKUP", "fl_{vty}_unfor_aggregate_by_lookup_widths", _I,
+     [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -250,6 +256,12 @@ def lookup_symbols():
     """The symbols FL_DECLARE_LOOKUP and FL_DECLARE_LOOKUP_U8 declare: for all four key types the two lookups with a payload of the
     key's own type and the two with a uint8_t payload (for u8 keys the same two functions under a second name)."""
     return _symbols("LOOKUP", "LOOKUP_U8")
+
+
+def aggregate_by_lookup_symbols():
+    """The symbols FL_DECLARE_AGGREGATE_BY_LOOKUP declares: for all four element types the fused lookup + grouped aggregate over a
+    uniform-width and over a mixed-width column pair."""
+    return _symbols("AGGREGATE_BY_LOOKUP")
 
 
 _LIB = None

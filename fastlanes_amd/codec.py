@@ -574,6 +574,36 @@ class FoR:
         return table, stats
 
     @staticmethod
+    def unfor_aggregate_by_lookup(width, packed, reference, key_width, key_packed, key_reference, lo, table, present=None, mask=None,
+                                  n_blocks=None, result=None, stats=None):
+        """GROUP BY a dimension attribute, fused (unfor_aggregate_by_lookup_widths' uniform form): every row `mask` keeps (None: every
+        row) with the key k = FoR.unfor_pack(key_width, key_packed, key_reference)[i] and j = (k - lo) mod 2^T updates group table[j]
+        (`table`: a CUDA uint8 tensor) with the value FoR.unfor_pack(width, packed, reference)[i] when j < len(table) and bit j of
+        `present` (a MemberSet with the window lo, len(table); None: every slot) is set, and is counted as a miss otherwise -- FoR.unfor_lookup
+        with a uint8 table followed by FoR.unfor_aggregate_by under the hits, with no code column and no hit mask written.  Returns
+        (result, stats): a CUDA int64[256, 4] tensor (`result` if given) of count, sum, min, max per group, every row written by every
+        call, and a CUDA int64[2] tensor holding uint64 bits, += (hits, kept rows that miss) (`stats` if given).  Device tier only.
+        n_blocks is only needed when both widths are 0 and there is no mask."""
+        src, ksrc = _Arg(packed), _Arg(key_packed)
+        ty = src.ty
+        if ksrc.ty != ty:
+            raise TypeError(f"the key column must have the value column's element type, got {ksrc.ty} and {ty}")
+        if not src.torch:
+            raise TypeError("unfor_aggregate_by_lookup is device tier (pass CUDA tensors)")
+        _same_tier(src, ksrc)
+        _check_width(ty, key_width, "unfor_aggregate_by_lookup")
+        n = _uniform_blocks(src, width, "unfor_aggregate_by_lookup", n_blocks, (key_packed if key_width else None, packed_len(ty, key_width)),
+                            (mask if _is_torch(mask) else None, 32))
+        if _uniform_blocks(ksrc, key_width, "unfor_aggregate_by_lookup", n) != n:
+            raise ValueError(f"the key column does not hold the value column's {n} blocks")
+        args, out = _aggregate_by_lookup_args("unfor_aggregate_by_lookup", src, n, lo, table, present, mask, result, stats)
+        aux, stride, _ = FoR._ref(src, ty, reference, n)
+        kaux, kstride, _ = FoR._ref(ksrc, ty, key_reference, n)
+        _launch(f"fl_{ty}_unfor_aggregate_by_lookup", src.x.device, width, src.ptr, aux.ptr, stride, key_width, ksrc.ptr, kaux.ptr, kstride,
+                *args, None)
+        return out
+
+    @staticmethod
     def unfor_compare_columns(width_a, a, a_reference, op, width_b, b, b_reference, *, signed=False, mask=None, combine="new", n_blocks=None,
                               output=None):
         """A predicate between two columns, chained through a mask: with va = FoR.unfor_pack(width_a, a block, a_reference)[i] and vb
@@ -1282,6 +1312,22 @@ def full_width_column(ty, n_blocks, device):
     return widths, offsets, references
 
 
+def _present_words(src, lo, n_slots, present):
+    """`present` of the lookups: None (every slot is present), or a MemberSet of the key column's type whose window is the table's
+    (lo, n_slots) -> its words on the column's device (None for an empty window: nothing is read)"""
+    if present is None:
+        return None
+    ty = src.ty
+    T = _lib.BITS[ty]
+    if not isinstance(present, MemberSet):
+        raise TypeError("present must be a MemberSet (member_set, or an unfor_set_build result)")
+    if present.ty != ty:
+        raise TypeError(f"present is a member set of {present.ty}, the key column of {ty}")
+    if (int(present.lo) & ((1 << T) - 1), present.bits) != (lo, n_slots):
+        raise ValueError(f"present has the window (lo={present.lo}, bits={present.bits}), the table (lo={lo}, slots={n_slots})")
+    return present.on(src.x.device) if n_slots else None
+
+
 def _lookup_args(src, n, lo, table, present, missing, mask, hit, output, stats):
     """What both lookup forms share behind the column: the entry's name suffix, the C arguments from `mask` to `stats`, and the three
     tensors the call returns.  `table.dtype` picks the entry: the key's own element size (payload U = T), or one byte (uint8)."""
@@ -1297,15 +1343,7 @@ def _lookup_args(src, n, lo, table, present, missing, mask, hit, output, stats):
     lo, n_slots = int(lo) & ((1 << T) - 1), tb.n
     if n_slots > min(1 << T, 1 << 32) or n_slots * (U // 8) >= 1 << 31:
         raise ValueError(f"table holds {n_slots} slots of {U // 8} bytes: at most {min(1 << T, 1 << 32)} slots and fewer than 2^31 bytes")
-    pr = None
-    if present is not None:
-        if not isinstance(present, MemberSet):
-            raise TypeError("present must be a MemberSet (member_set, or an unfor_set_build result)")
-        if present.ty != ty:
-            raise TypeError(f"present is a member set of {present.ty}, the key column of {ty}")
-        if (int(present.lo) & ((1 << T) - 1), present.bits) != (lo, n_slots):
-            raise ValueError(f"present has the window (lo={present.lo}, bits={present.bits}), the table (lo={lo}, slots={n_slots})")
-        pr = present.on(src.x.device) if n_slots else None
+    pr = _present_words(src, lo, n_slots, present)
     m = _select_mask(src, mask, n) if mask is not None else None
     out = _out(tb, output, uty, n * 1024, "unfor_lookup")
     _same_tier(src, out)
@@ -1447,6 +1485,64 @@ def unfor_aggregate_by_window_widths(widths, offsets, packed, references, key_wi
             _scalar(ty, table.lo), table.n_groups, *table._pointers(), stats.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_unfor_aggregate_by_window_widths")   # bitpacking.rs:93,126 unreachable!(); :111-113
     return table, stats
+
+
+def _aggregate_by_lookup_args(name, src, n, lo, table, present, mask, result, stats):
+    """What both fused forms share behind the two columns: the C arguments from `mask` to `stats`, and the two tensors the call returns.
+    The table is a uint8 tensor (one group code per slot); `present` is checked against its window as unfor_lookup_widths does."""
+    import torch
+    ty = src.ty
+    T = _lib.BITS[ty]
+    tb = _Arg(table)
+    _same_tier(src, tb)
+    if tb.x.dtype != torch.uint8:
+        raise TypeError(f"table must be a uint8 tensor (one of 256 group codes per slot), got {tb.x.dtype}")
+    lo, n_slots = int(lo) & ((1 << T) - 1), tb.n
+    if n_slots > min(1 << T, 1 << 32) or n_slots >= 1 << 31:
+        raise ValueError(f"table holds {n_slots} slots: at most {min(1 << T, 1 << 32)} slots and fewer than 2^31 bytes")
+    pr = _present_words(src, lo, n_slots, present)
+    m = _select_mask(src, mask, n) if mask is not None else None
+    dev = src.x.device
+    if result is None:
+        out = torch.empty((AGGREGATE_BY_GROUPS, 4), dtype=torch.int64, device=dev)
+    else:
+        out = _consumer_out(src, result, torch.int64, AGGREGATE_BY_GROUPS * 4, name).view(AGGREGATE_BY_GROUPS, 4)
+    if stats is None:
+        stats = torch.zeros(2, dtype=torch.int64, device=dev)
+    st = _block_words(stats, "stats", 2, 8, src, 1)[0]
+    args = (m.ptr if m is not None and n else None, n, _scalar(ty, lo), n_slots, tb.ptr if n_slots else None,
+            pr.data_ptr() if pr is not None else None, out.data_ptr(), st.ptr)
+    return args, (out, st.x)
+
+
+def unfor_aggregate_by_lookup_widths(widths, offsets, packed, references, key_widths, key_offsets, key_packed, key_references, lo, table,
+                                     present=None, mask=None, result=None, stats=None, check=True):
+    """GROUP BY a dimension attribute, fused: unfor_lookup_widths with a uint8 table followed by unfor_aggregate_by_widths under the
+    hits, in one pass over two mixed-width columns of one element type and block count, with no code column and no hit mask written
+    -- SELECT n_name, SUM(revenue) ... GROUP BY n_name through l_suppkey.  Every row `mask` keeps (32 words per block,
+    unfor_compare_widths' layout; None: every row) with the key k = unfor_pack_widths(key_widths, key_offsets, key_packed,
+    key_references)[i] and j = (k - lo) mod 2^T updates group table[j] with the value unfor_pack_widths(widths, offsets, packed,
+    references)[i] when j < len(table) and bit j of `present` is set (a MemberSet with the window lo, len(table) -- ValueError
+    otherwise; None: every slot is present), and is counted as a miss otherwise.  `table` is a CUDA uint8 tensor.  Returns
+    (result, stats): result is a CUDA int64[256, 4] tensor (`result` if given), row g = count, sum, min, max of group g as
+    FoR.unfor_aggregate_by's, every row written by every call; stats is a CUDA int64[2] tensor holding uint64 bits, += (hits, kept rows
+    that miss); `stats` if given, else a fresh zeroed one.  A block whose mask is empty reads nothing, a key block outside the window
+    reads neither column, a width-0 key block reads no key byte.  The per-block device checks of unfor_pack_widths run on BOTH
+    columns: a block that fails either contributes nothing; `check=True` reads the device error flag back (one sync) and raises,
+    `check=False` stays asynchronous."""
+    src, ksrc = _Arg(packed), _Arg(key_packed)
+    ty = src.ty
+    if ksrc.ty != ty:
+        raise TypeError(f"the key column must have the value column's element type, got {ksrc.ty} and {ty}")
+    n, lead = _widths_column("unfor_aggregate_by_lookup_widths", src, widths, offsets, ksrc, references=references)
+    kn, klead = _widths_column("unfor_aggregate_by_lookup_widths", ksrc, key_widths, key_offsets, src, references=key_references)
+    if kn != n:
+        raise ValueError(f"the key column holds {kn} blocks, the value column {n}")
+    args, out = _aggregate_by_lookup_args("unfor_aggregate_by_lookup_widths", src, n, lo, table, present, mask, result, stats)
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_unfor_aggregate_by_lookup_widths", src.x.device, *lead, *klead, *args, flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_unfor_aggregate_by_lookup_widths")   # bitpacking.rs:93,126 unreachable!(); :111-113 -- of either column
+    return out
 
 
 def unfor_compare_columns_widths(a_widths, a_offsets, a_packed, a_references, op, b_widths, b_offsets, b_packed, b_references, *,

@@ -22,6 +22,7 @@
 #include "fl_aggregate_by_columns.hpp"
 #include "fl_set_build.hpp"
 #include "fl_lookup.hpp"
+#include "fl_aggregate_by_lookup.hpp"
 #include "fl_aggregate_by_window.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
@@ -666,6 +667,77 @@ int run_unfor_lookup(const Column& col, const T* packed, const T* refs, size_t r
     return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
+// unfor_aggregate_by_lookup (fl_aggregate_by_lookup.hpp): unfor_lookup_u8 and unfor_aggregate_by in one pass -- a value column and a key
+// column of T of the same form, both uniform or both mixed, a u8 table over the window [key_lo, key_lo + n_slots - 1], 256 groups.  One
+// validator, one builder.  The validator's order is that of the two parents: the widths; n_slots (FL_ERR_INDEX, lookup_slots_refused with
+// a one-byte payload); `result` (written by EVERY call -- the init launch also answers an empty column -- so it is required before the
+// empty-column return), `table` (never read when n_slots == 0: the validator drops it and `present`, so they are neither read nor
+// checked) and the columns' pointers (FL_ERR_NULL; `mask`, `present` and `stats` may be NULL); alignment.  The persistent grid takes
+// the policy's waves and blocks per wavefront as run_unfor_aggregate_by does.
+struct LookupGroups {
+    const uint8_t* table;
+    const uint32_t* present;
+    void* result;
+    uint64_t* stats;
+};
+template <typename T>
+int aggregate_by_lookup_refusal(const Column& col, const T*& packed, const T* refs, const Column& kcol, const T*& keys, const T* key_refs,
+                                const uint32_t* mask, size_t n_blocks, uint64_t n_slots, LookupGroups& t)
+{
+    if ((!col.mixed && over_width<T>(col.width)) || (!kcol.mixed && over_width<T>(kcol.width))) return FL_ERR_WIDTH;
+    if (lookup_slots_refused(Elem<T>::BITS, n_slots, 1u)) return FL_ERR_INDEX;
+    if (!t.result) return FL_ERR_NULL;
+    if (n_blocks) {
+        if (n_slots == 0) {                                              // the empty window: never read, never checked
+            t.table = nullptr;
+            t.present = nullptr;
+        } else if (!t.table) {
+            return FL_ERR_NULL;
+        }
+        if (!block_consumer_column(col, packed, refs) || !block_consumer_column(kcol, keys, key_refs)) return FL_ERR_NULL;
+        if (misaligned(packed) || misaligned(keys) || misaligned(mask) || misaligned(t.present) || misaligned(t.table) || misaligned(t.stats))
+            return FL_ERR_ALIGN;
+    }
+    return misaligned(t.result) ? FL_ERR_ALIGN : FL_OK;
+}
+template <typename T>
+AggregateByLookupArgs aggregate_by_lookup_args(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
+                                               const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
+                                               uint64_t n_slots, const LookupGroups& t, uint32_t* err_flag, const WaveShape& sh)
+{
+    const ForPredicate p = set_window(Elem<T>::BITS, key_lo, n_slots);
+    AggregateByLookupArgs a;
+    widths_args<T>(a.val, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    widths_args<T>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    a.val_refs = refs;
+    a.key_refs = key_refs;
+    a.mask = mask;
+    a.table = t.table;
+    a.present = t.present;
+    a.result = static_cast<BlockAggregate*>(t.result);
+    a.stats = t.stats;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = p.none ? 1u : 0u;
+    a.table_bytes = (unsigned)n_slots;
+    a.present_bytes = t.present ? (unsigned)(4u * set_word_count(n_slots)) : 0u;
+    a.run = 0;
+    return a;
+}
+template <typename T>
+int run_unfor_aggregate_by_lookup(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
+                                  const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo, uint64_t n_slots,
+                                  LookupGroups t, uint32_t* err_flag, void* stream)
+{
+    if (const int rc = aggregate_by_lookup_refusal<T>(col, packed, refs, kcol, keys, key_refs, mask, n_blocks, n_slots, t); rc != FL_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipError_t e = launch_aggregate_by_init(static_cast<BlockAggregate*>(t.result), s); e != hipSuccess || n_blocks == 0) return hip_status(e);
+    const WaveShape sh = with_policy({0, 0u, 0u});
+    const AggregateByLookupArgs a =
+        aggregate_by_lookup_args<T>(col, packed, refs, ref_stride, kcol, keys, key_refs, key_ref_stride, mask, n_blocks, key_lo, n_slots, t, err_flag, sh);
+    return hip_status(aggregate_by_lookup_launcher<T>()(a, sh.waves, s));
+}
+
 // unfor_compare_columns (fl_for_compare_columns.hpp): two columns of T of the same form, both uniform or both mixed.  The six ops become
 // one base relation, "swap the columns" and "invert" here, once per call (fl_columns_decide.hpp: columns_relation); the swap is done
 // here, so the kernel's column a is always the base relation's left side.  The launch shape and the order of the checks are those of
@@ -1301,6 +1373,29 @@ FL_DEFINE_LOOKUP_U8(uint8_t, u8)
 FL_DEFINE_LOOKUP_U8(uint16_t, u16)
 FL_DEFINE_LOOKUP_U8(uint32_t, u32)
 FL_DEFINE_LOOKUP_U8(uint64_t, u64)
+
+#define FL_DEFINE_AGGREGATE_BY_LOOKUP(T, S)                                                               \
+    int fl_##S##_unfor_aggregate_by_lookup(unsigned w, const T* in, const T* r, size_t rs, unsigned kw, const T* k, const T* kr, size_t krs, \
+                                           const uint32_t* mask, size_t n, T lo, uint64_t ns, const uint8_t* tb, const uint32_t* pr, void* res, \
+                                           uint64_t* st, uint32_t* ef, void* s)                           \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, in, r, k, kr, mask, tb, pr, res, st, ef);                                       \
+        return run_unfor_aggregate_by_lookup<T>({false, w}, in, r, rs, {false, kw}, k, kr, krs, mask, n, lo, ns, {tb, pr, res, st}, ef, s); \
+    }                                                                                                     \
+    int fl_##S##_unfor_aggregate_by_lookup_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, \
+                                                  const uint8_t* kw, const uint64_t* ko, const T* k, size_t kb, const T* kr, size_t krs, \
+                                                  const uint32_t* mask, size_t n, T lo, uint64_t ns, const uint8_t* tb, const uint32_t* pr, \
+                                                  void* res, uint64_t* st, uint32_t* ef, void* s)         \
+    {                                                                                                     \
+        FL_DEVICE_TIER(s, w, o, pk, r, kw, ko, k, kr, mask, tb, pr, res, st, ef);                         \
+        return run_unfor_aggregate_by_lookup<T>({true, 0, w, o, pb}, pk, r, rs, {true, 0, kw, ko, kb}, k, kr, krs, mask, n, lo, ns, \
+                                                {tb, pr, res, st}, ef, s);                                \
+    }
+
+FL_DEFINE_AGGREGATE_BY_LOOKUP(uint8_t, u8)
+FL_DEFINE_AGGREGATE_BY_LOOKUP(uint16_t, u16)
+FL_DEFINE_AGGREGATE_BY_LOOKUP(uint32_t, u32)
+FL_DEFINE_AGGREGATE_BY_LOOKUP(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                               \
     int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \

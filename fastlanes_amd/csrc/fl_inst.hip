@@ -18,6 +18,7 @@
 //   22 unfor_set_build (the member set of the values a mask keeps of such a column, ORed into a window's bitmap: the build side of unfor_compare_in; fl_set_build.hpp)
 //   23 unfor_aggregate_by_window (count / sum / min / max per key of a dense window of the key domain, value and key column FoR-packed and of one type, accumulated into the caller's arrays; fl_aggregate_by_window.hpp)
 //   24 unfor_lookup (a dimension attribute of the key's own type or u8 fetched through such a column inside a dense window of the key domain under a mask, written in full-width packed order: the probe side of a payload join; fl_lookup.hpp)
+//   25 unfor_aggregate_by_lookup (count / sum / min / max per u8 attribute fetched through a key column inside a dense window of the key domain, value and key column FoR-packed and of one type: unfor_lookup_u8 and unfor_aggregate_by in one pass with no per-row output; fl_aggregate_by_lookup.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -36,6 +37,7 @@
 #include "fl_set_build.hpp"
 #include "fl_aggregate_by_window.hpp"
 #include "fl_lookup.hpp"
+#include "fl_aggregate_by_lookup.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -193,7 +195,9 @@ template <> lookup_launch_t lookup_launcher<T>(unsigned payload_bytes, int tier)
     }
     return nullptr;
 }
+#elif FL_FAMILY == 25
+template <> aggregate_by_lookup_launch_t aggregate_by_lookup_launcher<T>() { return &launch_aggregate_by_lookup<T>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..24"
+#error "FL_FAMILY must be 0..6 or 8..25"
 #endif
 }  // namespace fl

@@ -914,8 +914,8 @@ FL_DECLARE_AGGREGATE_BY_WINDOW(uint64_t, u64)
  * (`in` / `packed` may be NULL only when no byte of it can be read: width 0, or packed_bytes == 0); the packed column, `mask`,
  * `hit_mask`, `present`, `table`, `out` and `stats` are 16-byte aligned (FL_ERR_ALIGN).
  * Out of scope: payload types other than T and uint8_t; several tables per launch; sparse or hashed keys (a window is dense); Delta
- * columns; the host tier; tables of 2^31 bytes or more; a fused GROUP BY-through-lookup kernel (lookup -> fl_<ty>_unfor_aggregate_by
- * serves it; whether fusing pays is a later change's question).
+ * columns; the host tier; tables of 2^31 bytes or more.  (The fused GROUP BY through a uint8_t lookup, with no code column and no hit
+ * mask written, is fl_<ty>_unfor_aggregate_by_lookup below.)
  * (Declared by two macros of their own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol
  * lists are pinned surfaces.)
  */
@@ -958,6 +958,73 @@ FL_DECLARE_LOOKUP_U8(uint8_t, u8)
 FL_DECLARE_LOOKUP_U8(uint16_t, u16)
 FL_DECLARE_LOOKUP_U8(uint32_t, u32)
 FL_DECLARE_LOOKUP_U8(uint64_t, u64)
+
+/*
+ * EXTENSION: GROUP BY A DIMENSION ATTRIBUTE, FUSED -- fl_<ty>_unfor_lookup_u8 and fl_<ty>_unfor_aggregate_by in one
+ * pass: SUM(revenue) GROUP BY n_name reached through l_suppkey (TPC-H Q5, Q7, Q8, Q10), GROUP BY d_year, p_brand through lo_orderdate
+ * and lo_partkey (Star Schema Benchmark Q2 on), with NO per-row output: no code column, no hit mask.  The value column and the key
+ * column have the SAME element type T and the same n_blocks, as in fl_<ty>_unfor_aggregate_by_window.  Defined as the composition (all
+ * key arithmetic mod 2^T)
+ *     result[g] = identity {0, 0, UINT64_MAX, 0}                 for g = 0..255   (every slot written by every call)
+ *     for every block b, every i in 0..1023 with bit i of block b of `mask` set (mask == NULL: every i):
+ *         val = unfor_pack::<W_b >(value block b, references[b*reference_stride])[i]        zero-extended to uint64  (ffor.rs:38-50)
+ *         key = unfor_pack::<KW_b>(key block b, key_references[b*key_reference_stride])[i]
+ *         j   = (key - key_lo) mod 2^T
+ *         hit = j < n_slots and (present == NULL or bit j of present)
+ *         hit:  g = table[j];  result[g] = combine(result[g], {1, val, val, val});  hits += 1
+ *         else: misses += 1
+ *     stats[0] += hits;  stats[1] += misses        -- stats: DEVICE uint64[2], may be NULL; it accumulates, as everywhere else
+ * `table` is DEVICE uint8_t[n_slots], 0 <= n_slots <= min(2^T, 2^32) and n_slots < 2^31; `present` has the layout of
+ * fl_<ty>_unfor_lookup's (bits past n_slots are ignored) and may be NULL: every slot is present.  `result`, combine, the identity and
+ * the mask layout are exactly those of fl_<ty>_unfor_aggregate_by: 256 fl_block_aggregate, written by every call.  The call equals,
+ * bit for bit in `result` and in `stats`, fl_<ty>_unfor_lookup_u8[_widths] into a temporary with its hit mask followed by
+ * fl_<ty>_unfor_aggregate_by[_widths] with that temporary as the full-width u8 key column and mask = the hits.  Integer add, min and max
+ * commute: the result is bitwise reproducible.
+ * A block whose mask is empty reads nothing; a block whose key reference and key width put all its keys outside the window (n_slots
+ * == 0 among them) reads neither column and no table byte and counts its kept rows as misses; a key block of width 0 inside the window
+ * takes one table read (and at most one `present` bit): an absent slot counts its kept rows as misses without reading the value block,
+ * a present one folds the value block's aggregate into group table[c] without reading a key byte.  Every other block decodes both
+ * columns and gathers one table byte per kept row inside the window through one bounded buffer descriptor (default cache policy; there
+ * is no LDS copy of the table: the LDS holds the 256 groups).  The mixed-width form runs the per-block device checks of
+ * fl_<ty>_unfor_compare_widths on BOTH columns: a failing block is skipped, its FL_DEVERR_* bits are ORed into *err_flag, neither
+ * column is read and it contributes nothing to `result` or to stats.  The call is asynchronous on `stream`, allocates nothing and uses
+ * no scratch memory.
+ * width or key_width > T is FL_ERR_WIDTH (also for an empty column); n_slots above min(2^T, 2^32), or n_slots >= 2^31, FL_ERR_INDEX;
+ * result == NULL, table == NULL with n_slots > 0 or any required column pointer NULL FL_ERR_NULL (`in` / `packed` / `keys` may be NULL
+ * only when no byte of it can be read: width 0, or its packed bytes == 0); the packed columns, `mask`, `present`, `table`, `result` and
+ * `stats` are 16-byte aligned (FL_ERR_ALIGN); n_blocks == 0 is FL_OK: `result` receives the 256 identities, as
+ * fl_<ty>_unfor_aggregate_by's, and stats is untouched.
+ * Out of scope: a value type different from the key type; payloads wider than uint8_t or more than 256 groups
+ * (fl_<ty>_unfor_aggregate_by_window after a T-payload lookup serves those); several tables, or an a o b expression, per launch; an LDS
+ * copy of the dimension table; sparse or hashed keys; Delta columns; the host tier; tables of 2^31 bytes or more.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_AGGREGATE_BY_LOOKUP(T, S)                                                              \
+    int fl_##S##_unfor_aggregate_by_lookup(unsigned width, const T *in, const T *references, size_t reference_stride, \
+                                           unsigned key_width, const T *keys, const T *key_references,    \
+                                           size_t key_reference_stride, const uint32_t *mask /* NULL: every row */, \
+                                           size_t n_blocks, T key_lo, uint64_t n_slots,                   \
+                                           const uint8_t *table /* NULL with n_slots 0 */,                \
+                                           const uint32_t *present /* may be NULL */,                     \
+                                           void *result /* fl_block_aggregate[256] */,                    \
+                                           uint64_t *stats /* may be NULL */, uint32_t *err_flag, void *stream); \
+    int fl_##S##_unfor_aggregate_by_lookup_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                                  size_t packed_bytes, const T *references, size_t reference_stride, \
+                                                  const uint8_t *key_widths, const uint64_t *key_offsets, \
+                                                  const T *keys, size_t keys_bytes,                       \
+                                                  const T *key_references, size_t key_reference_stride,   \
+                                                  const uint32_t *mask /* NULL: every row */, size_t n_blocks, \
+                                                  T key_lo, uint64_t n_slots,                             \
+                                                  const uint8_t *table /* NULL with n_slots 0 */,         \
+                                                  const uint32_t *present /* may be NULL */,              \
+                                                  void *result /* fl_block_aggregate[256] */,             \
+                                                  uint64_t *stats /* may be NULL */, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_AGGREGATE_BY_LOOKUP(uint8_t, u8)
+FL_DECLARE_AGGREGATE_BY_LOOKUP(uint16_t, u16)
+FL_DECLARE_AGGREGATE_BY_LOOKUP(uint32_t, u32)
+FL_DECLARE_AGGREGATE_BY_LOOKUP(uint64_t, u64)
 
 #ifdef __cplusplus
 }

@@ -73,6 +73,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_lookup_widths = fl_##S##_unfor_lookup_widths;                    \
         static constexpr auto unfor_lookup_u8 = fl_##S##_unfor_lookup_u8;                            \
         static constexpr auto unfor_lookup_u8_widths = fl_##S##_unfor_lookup_u8_widths;              \
+        static constexpr auto unfor_aggregate_by_lookup = fl_##S##_unfor_aggregate_by_lookup;        \
+        static constexpr auto unfor_aggregate_by_lookup_widths = fl_##S##_unfor_aggregate_by_lookup_widths; \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -258,6 +260,16 @@ template <typename T> struct FoR : BitPacking<T> {
                                        const std::uint32_t* d_present, std::uint8_t missing, std::uint8_t* d_out, std::uint32_t* d_hit_mask = nullptr,
                                        std::uint64_t* d_stats = nullptr, void* stream = nullptr)
     { detail::check(A::unfor_lookup_u8((unsigned)width, d_packed, d_refs, ref_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, missing, d_out, d_hit_mask, d_stats, stream), "unfor_lookup_u8_device"); }
+    // unfor_lookup_u8_device and unfor_aggregate_by_device in one pass, with no code column and no hit mask written: d_result[g], g = 0 ..
+    // 255 (all written by every call), = count / sum / min / max of the values of the rows d_mask keeps (nullptr: every row) whose key k of
+    // the key column (the value column's own type) has j = (k - key_lo) mod 2^T < n_slots, bit j of d_present set (nullptr: every slot)
+    // and d_table[j] == g; d_stats (nullptr: not counted) += {hits, kept rows that miss}
+    static void unfor_aggregate_by_lookup_device(std::size_t width, const T* d_packed, const T* d_refs, std::size_t ref_stride, std::size_t key_width,
+                                                 const T* d_keys, const T* d_key_refs, std::size_t key_ref_stride, const std::uint32_t* d_mask,
+                                                 std::size_t n_blocks, T key_lo, std::uint64_t n_slots, const std::uint8_t* d_table,
+                                                 const std::uint32_t* d_present, fl_block_aggregate* d_result, std::uint64_t* d_stats = nullptr,
+                                                 std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::unfor_aggregate_by_lookup((unsigned)width, d_packed, d_refs, ref_stride, (unsigned)key_width, d_keys, d_key_refs, key_ref_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, d_result, d_stats, d_err_flag, stream), "unfor_aggregate_by_lookup_device"); }
     // a <op> b between two FoR-packed columns of T with the same block count (signed: of the two's-complement values), joined with the
     // mask so far as unfor_compare_range_device does; a block pair the references and widths decide reads neither column
     static void unfor_compare_columns_device(std::size_t width_a, const T* d_a, const T* d_a_refs, std::size_t a_ref_stride, std::size_t width_b,
@@ -576,6 +588,18 @@ inline void unfor_lookup_u8_widths_device(const std::uint8_t* d_widths, const st
                                           std::uint8_t missing, std::uint8_t* d_out, std::uint32_t* d_hit_mask = nullptr, std::uint64_t* d_stats = nullptr,
                                           std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_lookup_u8_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, missing, d_out, d_hit_mask, d_stats, d_err_flag, stream), "unfor_lookup_u8_widths"); }
+// ... and the u8 lookup fused with the grouped aggregate over two mixed-width columns of T with the same block count: d_result[g] (256
+// slots, all written by every call) = count / sum / min / max of the values of the kept rows whose key hits a slot of d_table holding g,
+// d_stats += {hits, kept rows that miss}; both columns get unfor_pack_widths' device checks, a block that fails either contributes nothing
+template <typename T>
+inline void unfor_aggregate_by_lookup_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                                    const T* d_references, std::size_t reference_stride, const std::uint8_t* d_key_widths,
+                                                    const std::uint64_t* d_key_offsets, const T* d_keys, std::size_t keys_bytes,
+                                                    const T* d_key_references, std::size_t key_reference_stride, const std::uint32_t* d_mask,
+                                                    std::size_t n_blocks, T key_lo, std::uint64_t n_slots, const std::uint8_t* d_table,
+                                                    const std::uint32_t* d_present, fl_block_aggregate* d_result, std::uint64_t* d_stats = nullptr,
+                                                    std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::unfor_aggregate_by_lookup_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, d_key_widths, d_key_offsets, d_keys, keys_bytes, d_key_references, key_reference_stride, d_mask, n_blocks, key_lo, n_slots, d_table, d_present, d_result, d_stats, d_err_flag, stream), "unfor_aggregate_by_lookup_widths"); }
 // ... and a predicate between two mixed-width columns of T with the same block count, a <op> b (signed: of the two's-complement values),
 // chained the same way; both columns get unfor_pack_widths' device checks, a block that fails either keeps its mask words
 template <typename T>
