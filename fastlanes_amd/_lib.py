@@ -165,6 +165,10 @@ _SIGNATURES = (
     ("AGGREGATE_BY_LOOKUP", "fl_{vty}_unfor_aggregate_by_lookup", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
     ("AGGREGATE_BY_LOOKUP", "fl_{vty}_unfor_aggregate_by_lookup_widths", _I,
      [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
+    # FL_DECLARE_DELTA_COMPARE_RANGE (device tier): interval predicates over DELTA-packed columns, chained through a mask ({vty} as
+    # above: these rows' refusals are pinned by tests/test_delta_compare_range_cpu.py)
+    ("DELTA_COMPARE_RANGE", "fl_{vty}_undelta_compare_range", _I, [_U, _P, _P, _T, _T, _I, _P, _Z, _P, _P]),
+    ("DELTA_COMPARE_RANGE", "fl_{vty}_undelta_compare_range_widths", _I, [_P, _P, _P, _Z, _P, _T, _T, _I, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -262,6 +266,12 @@ def aggregate_by_lookup_symbols():
     """The symbols FL_DECLARE_AGGREGATE_BY_LOOKUP declares: for all four element types the fused lookup + grouped aggregate over a
     uniform-width and over a mixed-width column pair."""
     return _symbols("AGGREGATE_BY_LOOKUP")
+
+
+def delta_compare_range_symbols():
+    """The symbols FL_DECLARE_DELTA_COMPARE_RANGE declares: for all four element types the interval predicate over a uniform-width and
+    over a mixed-width Delta-packed column."""
+    return _symbols("DELTA_COMPARE_RANGE")
 
 
 _LIB = None

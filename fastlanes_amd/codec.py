@@ -812,6 +812,33 @@ class Delta:
         return Delta._go("undelta_pack_untranspose", width, input, base, output, lambda ty: packed_len(ty, width))
 
     @staticmethod
+    def undelta_compare_range(width, packed, base, lo, hi, mask=None, combine="new", n_blocks=None, output=None):
+        """Interval predicate straight from a Delta-packed column, chained through a mask: with v = the values
+        Delta.undelta_pack_untranspose(width, packed, base) yields (ORIGINAL row order) and all arithmetic mod 2^T, hit = ((v - lo) mod 2^T)
+        <= ((hi - lo) mod 2^T) -- the cyclic interval [lo, hi] of FoR.unfor_compare_range, whose masks, `combine` names and in-place rule
+        (`output` may be `mask` itself) these are: the result heads or joins any chain of the FoR consumers.  `base` holds LANES = 1024/T
+        elements per block.  No decoded column is written: a block whose bases and width decide the interval (on a sorted column nearly
+        every block), a width-0 block, a block whose `mask` is all zero under "and" and one whose `mask` is all ones under "or" are
+        answered without reading their packed bytes.  Device tier only; returns a CUDA int32 tensor of 32 words per block (`output` if
+        given).  n_blocks is only needed for width == 0 (default: from `base`)."""
+        import torch
+        cb = _range_combine(combine, mask)
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("undelta_compare_range is device tier (pass CUDA tensors)")
+        lanes = 1024 // _lib.BITS[ty]
+        if n_blocks is None and width == 0:
+            n_blocks = _numel(base) // lanes
+        n = _uniform_blocks(src, width, "undelta_compare_range", n_blocks, (mask if cb and _is_torch(mask) else None, 32), (output, 32))
+        b, _ = _block_bases(src, ty, base, n)
+        m = _select_mask(src, mask, n) if cb else None
+        out = _consumer_out(src, output, torch.int32, n * 32, "undelta_compare_range")
+        _launch(f"fl_{ty}_undelta_compare_range", src.x.device, width, src.ptr, b.ptr, _scalar(ty, lo), _scalar(ty, hi), cb,
+                m.ptr if m is not None and n else None, n, out.data_ptr())
+        return out
+
+    @staticmethod
     def transpose_delta_pack(width, input, base, output=None):
         """== BitPacking.pack(width, Delta.delta(Transpose.transpose(input), base)): encodes straight
         from the ORIGINAL element order.  Device tier only."""
@@ -1797,6 +1824,31 @@ def undelta_pack_widths(widths, offsets, packed, base, output=None, check=True, 
     out = _out(src, output, ty, n * 1024, method)
     _widths_call(method, ty, widths, offsets, src, out, check, aux)
     return out.x
+
+
+def undelta_compare_range_widths(widths, offsets, packed, base, lo, hi, mask=None, combine="new", output=None, check=True):
+    """Delta.undelta_compare_range over a mixed-width column: the cyclic interval [lo, hi] (mod 2^T; predicate_interval gives a
+    comparison's) over the values undelta_pack_widths(widths, offsets, packed, base, untranspose=True) yields, joined with the mask so
+    far exactly as unfor_compare_range_widths joins it -- the same masks (32 words per block, bit i = original row i), the same
+    `combine` names, `output` may be `mask` itself.  A block its bases and width decide, a width-0 block and a block its `mask` already
+    decides read no packed byte.  The per-block device checks of unfor_compare_widths, with the same contract: a block that fails them
+    is skipped (its 32 mask words are left as they were); `check=True` reads the device error flag back (one sync) and raises,
+    `check=False` stays asynchronous."""
+    import torch
+    cb = _range_combine(combine, mask)
+    if cb and _is_torch(mask) and _is_torch(widths) and mask.numel() != 32 * widths.numel():
+        raise ValueError(f"mask holds {mask.numel()} words, expected 32 per block = {32 * widths.numel()}")
+    src = _Arg(packed)
+    ty = src.ty
+    n, lead = _widths_column("undelta_compare_range_widths", src, widths, offsets)
+    b, aux = _block_bases(src, ty, base, n)
+    m = _select_mask(src, mask, n) if cb else None
+    out = _consumer_out(src, output, torch.int32, n * 32, "undelta_compare_range_widths")
+    flag = _Flag(check, src.x.device)
+    _launch(f"fl_{ty}_undelta_compare_range_widths", src.x.device, *lead, *aux, _scalar(ty, lo), _scalar(ty, hi), cb,
+            m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
+    flag.raise_if_set(f"fl_{ty}_undelta_compare_range_widths")  # bitpacking.rs:93,126 unreachable!(); :111-113
+    return out
 
 
 def transpose_delta_pack_widths(widths, offsets, input, base, output, check=True):

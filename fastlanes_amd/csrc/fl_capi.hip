@@ -23,6 +23,7 @@
 #include "fl_set_build.hpp"
 #include "fl_lookup.hpp"
 #include "fl_aggregate_by_lookup.hpp"
+#include "fl_delta_compare_range.hpp"
 #include "fl_aggregate_by_window.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
@@ -457,6 +458,35 @@ int run_unfor_compare_range(const Column& col, const T* packed, const T* refs, s
     a.mask_in = reinterpret_cast<const char*>(mask_in);
     a.combine = (unsigned)combine;
     return hip_status(for_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// undelta_compare_range (fl_delta_compare_range.hpp): run_unfor_compare_range over a Delta-packed column -- `bases` (LANES per block, 128
+// bytes, read as 16-byte cells) stands where the references stood.  The same checks in the same order, `bases` among the required and
+// the aligned pointers; one block per wavefront for every type, at unfor_pack_widths' occupancy; `mask` may be `mask_in`.
+template <typename T>
+int run_undelta_compare_range(const Column& col, const T* packed, const T* bases, T lo, T hi, int combine, const uint32_t* mask_in,
+                              size_t n_blocks, uint32_t* mask, uint32_t* err_flag, void* stream)
+{
+    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
+    if (combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
+    if (n_blocks == 0) return FL_OK;
+    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
+    else if (!mask_in) return FL_ERR_NULL;
+    if (!block_consumer_column(col, packed, bases) || !mask) return FL_ERR_NULL;
+    if (misaligned(packed) || misaligned(bases) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
+    const ForPredicate p = for_range_predicate(Elem<T>::BITS, lo, hi);
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), 1u, 0u});
+    DeltaRangeArgs a;
+    widths_args<T>(a, col, packed, nullptr, nullptr, 0, col.mixed ? err_flag : nullptr, n_blocks, sh);
+    a.mask = reinterpret_cast<char*>(mask);
+    a.cmp_refs = nullptr;
+    a.cmp_a = p.a;
+    a.cmp_s = p.s;
+    a.cmp_none = 0u;
+    a.mask_in = reinterpret_cast<const char*>(mask_in);
+    a.combine = (unsigned)combine;
+    a.bases = reinterpret_cast<const char*>(bases);
+    return hip_status(delta_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // unfor_compare_in: run_unfor_compare_range with the member set's window as the predicate and its bitmap beside it
@@ -1409,6 +1439,19 @@ FL_DEFINE_FOR_COMPARE_RANGE(uint8_t, u8)
 FL_DEFINE_FOR_COMPARE_RANGE(uint16_t, u16)
 FL_DEFINE_FOR_COMPARE_RANGE(uint32_t, u32)
 FL_DEFINE_FOR_COMPARE_RANGE(uint64_t, u64)
+
+#define FL_DEFINE_DELTA_COMPARE_RANGE(T, S)                                                             \
+    int fl_##S##_undelta_compare_range(unsigned w, const T* in, const T* b, T lo, T hi, int cb, const uint32_t* mi, size_t n, uint32_t* mask, \
+                                       void* s)                                                           \
+    { FL_DEVICE_TIER(s, in, b, mi, mask); return run_undelta_compare_range<T>({false, w}, in, b, lo, hi, cb, mi, n, mask, nullptr, s); } \
+    int fl_##S##_undelta_compare_range_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* b, T lo, T hi, int cb, \
+                                              const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
+    { FL_DEVICE_TIER(s, w, o, pk, b, mi, mask, ef); return run_undelta_compare_range<T>({true, 0, w, o, pb}, pk, b, lo, hi, cb, mi, n, mask, ef, s); }
+
+FL_DEFINE_DELTA_COMPARE_RANGE(uint8_t, u8)
+FL_DEFINE_DELTA_COMPARE_RANGE(uint16_t, u16)
+FL_DEFINE_DELTA_COMPARE_RANGE(uint32_t, u32)
+FL_DEFINE_DELTA_COMPARE_RANGE(uint64_t, u64)
 
 #define FL_DEFINE_FOR_COMPARE_IN(T, S)                                                                    \
     int fl_##S##_unfor_compare_in(unsigned w, const T* in, const T* r, size_t rs, T lo, uint64_t sb, const uint32_t* sw, int ng, int cb, \

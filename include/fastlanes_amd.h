@@ -1026,6 +1026,45 @@ FL_DECLARE_AGGREGATE_BY_LOOKUP(uint16_t, u16)
 FL_DECLARE_AGGREGATE_BY_LOOKUP(uint32_t, u32)
 FL_DECLARE_AGGREGATE_BY_LOOKUP(uint64_t, u64)
 
+/*
+ * EXTENSION: INTERVAL PREDICATES ON DELTA-PACKED COLUMNS -- WHERE l_shipdate BETWEEN a AND b on the sorted or nearly
+ * sorted columns (dates, timestamps, clustered keys) a FastLanes writer stores Delta-coded, with no decoded column written or read back.
+ * Defined as the composition (all arithmetic mod 2^T)
+ *     v[b]      = untranspose(undelta_pack::<W_b>(block b, bases[b*LANES .. b*LANES + LANES]))    (delta.rs:47-63, transpose.rs:17-22)
+ *     hit[b][i] = ((v[b][i] - lo) mod 2^T) <= ((hi - lo) mod 2^T)              -- the cyclic interval [lo, hi]
+ *     FL_MASK_NEW: mask[b] = hit[b]   (mask_in ignored, may be NULL)
+ *     FL_MASK_AND: mask[b] = mask_in[b] & hit[b]          FL_MASK_OR: mask[b] = mask_in[b] | hit[b]
+ * i is the ORIGINAL row (the order fl_<ty>_undelta_pack_untranspose writes); the masks, the interval, `combine` and the in-place rule
+ * (`mask` may be `mask_in` itself, any other overlap is the caller's error) are exactly those of fl_<ty>_unfor_compare_range, so the
+ * result heads or joins any chain of the FoR consumers.  `bases` holds LANES = 1024 / T elements per block (128 bytes), as for
+ * fl_<ty>_undelta_pack.  Every valid block's 128 mask bytes are always written.
+ * A block is answered without reading its packed bytes when `combine` is AND and its mask_in is all zero or `combine` is OR and its
+ * mask_in is all ones; when its bases and width decide it -- with c_l = (base_l - lo) mod 2^T, s = (hi - lo) mod 2^T and reach = T *
+ * (2^W - 1): every c_l <= s and max c_l + reach <= s (all rows hit), or every c_l > s and max c_l + reach <= 2^T - 1 (none does); and
+ * when its width is 0 (each lane's T rows repeat its base).  On a sorted column that is almost every block.  The mixed-width form runs
+ * the per-block device checks of fl_<ty>_unfor_compare_widths with the same contract: a failing block is skipped, its FL_DEVERR_* bit
+ * is ORed into *err_flag, its 32 mask words are left as they were.  Asynchronous on `stream`; allocates nothing, uses no scratch memory.
+ * width > T is FL_ERR_WIDTH (also for an empty column); a `combine` outside the enum FL_ERR_INDEX; n_blocks == 0 FL_OK; mask_in ==
+ * NULL with AND / OR, or any other required pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only when no byte can be read:
+ * width 0, or packed_bytes == 0); the packed column, `bases`, `mask` and `mask_in` are 16-byte aligned (FL_ERR_ALIGN).
+ * Out of scope: masks in transposed order; Delta forms of select and the aggregates; the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_DELTA_COMPARE_RANGE(T, S)                                                              \
+    int fl_##S##_undelta_compare_range(unsigned width, const T *in, const T *bases, T lo, T hi, int combine, \
+                                       const uint32_t *mask_in /* NULL with FL_MASK_NEW */, size_t n_blocks, \
+                                       uint32_t *mask, void *stream);                                     \
+    int fl_##S##_undelta_compare_range_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                              size_t packed_bytes, const T *bases, T lo, T hi, int combine, \
+                                              const uint32_t *mask_in /* NULL with FL_MASK_NEW */, size_t n_blocks, \
+                                              uint32_t *mask, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_DELTA_COMPARE_RANGE(uint8_t, u8)
+FL_DECLARE_DELTA_COMPARE_RANGE(uint16_t, u16)
+FL_DECLARE_DELTA_COMPARE_RANGE(uint32_t, u32)
+FL_DECLARE_DELTA_COMPARE_RANGE(uint64_t, u64)
+
 #ifdef __cplusplus
 }
 #endif

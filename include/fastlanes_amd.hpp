@@ -75,6 +75,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_lookup_u8_widths = fl_##S##_unfor_lookup_u8_widths;              \
         static constexpr auto unfor_aggregate_by_lookup = fl_##S##_unfor_aggregate_by_lookup;        \
         static constexpr auto unfor_aggregate_by_lookup_widths = fl_##S##_unfor_aggregate_by_lookup_widths; \
+        static constexpr auto undelta_compare_range = fl_##S##_undelta_compare_range;                \
+        static constexpr auto undelta_compare_range_widths = fl_##S##_undelta_compare_range_widths;  \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -339,6 +341,12 @@ template <typename T> struct Delta : BitPacking<T> {
     static void undelta_pack_untranspose_device(std::size_t width, const T* d_in, const T* d_bases, T* d_out,
                                                 std::size_t n_blocks, void* stream = nullptr)
     { detail::check(A::undelta_pack_untranspose((unsigned)width, d_in, d_bases, d_out, n_blocks, stream), "undelta_pack_untranspose_device"); }
+    // the cyclic interval [lo, hi] (mod 2^T) over the values undelta_pack_untranspose_device yields (ORIGINAL row order), joined with
+    // the mask so far exactly as FoR<T>::unfor_compare_range_device joins it (the same masks; d_mask may be d_mask_in): no decoded
+    // column is written, a block its bases and width decide reads no packed byte
+    static void undelta_compare_range_device(std::size_t width, const T* d_packed, const T* d_bases, T lo, T hi, fl_mask_combine combine,
+                                             const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
+    { detail::check(A::undelta_compare_range((unsigned)width, d_packed, d_bases, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, stream), "undelta_compare_range_device"); }
     static void transpose_delta_pack_device(std::size_t width, const T* d_in, const T* d_bases, T* d_out,
                                             std::size_t n_blocks, void* stream = nullptr)
     { detail::check(A::transpose_delta_pack((unsigned)width, d_in, d_bases, d_out, n_blocks, stream), "transpose_delta_pack_device"); }
@@ -542,6 +550,13 @@ inline void unfor_compare_range_widths_device(const std::uint8_t* d_widths, cons
                                               const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask,
                                               std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::unfor_compare_range_widths(d_widths, d_offsets, d_packed, packed_bytes, d_references, reference_stride, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "unfor_compare_range_widths"); }
+// ... and the same interval over a mixed-width DELTA-packed column (d_bases: LANES per block), the values in original row order: the
+// head of such a chain on a sorted column; the same device checks, a failing block keeps its mask words
+template <typename T>
+inline void undelta_compare_range_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                                const T* d_bases, T lo, T hi, fl_mask_combine combine, const std::uint32_t* d_mask_in,
+                                                std::size_t n_blocks, std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::undelta_compare_range_widths(d_widths, d_offsets, d_packed, packed_bytes, d_bases, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "undelta_compare_range_widths"); }
 // ... and set membership chained the same way: mask = [d_mask_in &, |] (value in the member set: a window of set_bits values from set_lo,
 // one bitmap bit each; negate: NOT IN); a block outside the window, or one the mask so far has decided, is not read
 template <typename T>
