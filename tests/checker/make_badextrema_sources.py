@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Makes the KNOWN-BAD sources of `make -C fastlanes_amd/csrc BADEXTREMA=1` (-> fastlanes_amd/libfastlanes_amd_badextrema.so): a copy
-of the library's sources with four defects in the kernels that take a minimum or a maximum, one per kernel family.  Test scaffolding:
+of the library's sources with ten defects in the kernels that take a minimum, a maximum or a sum.  Test scaffolding:
 the product headers carry none of this.
 
     python tests/checker/make_badextrema_sources.py <csrc dir> <output dir>
@@ -19,8 +19,24 @@ profiles/extrema_known_bad.txt):
    56-bit values never do.
 4. for_widths (fl_scan.hpp: k_for_widths): a span of exactly 2^k, k >= 17, gets k bits instead of k + 1.  The encoder-chain test masks
    its values to k bits; random pairs of u32 / u64 give a power of two once in 2^27.
-Never loaded by anything but `FL_LIB=.../libfastlanes_amd_badextrema.so pytest tests/test_gpu_extrema.py ...` and the older tests the
-profile names.  Every replacement below must match the current source exactly once, or this script fails: a refactor has to carry
+The expression and grouped aggregates (tests/expr_extrema_data.py, tests/test_gpu_expr_extrema.py, tests/test_gpu_group_extrema.py,
+profiles/expr_extrema_known_bad.txt), narrowed in the same way against their own older tests:
+5. unfor_aggregate_columns (fl_aggregate_columns.hpp: expr_lds_image), u16 a + b with column b at W >= 15: a masked-off row wins the
+   minimum when it is exactly one below the lane's minimum so far -- the second element of the lane's first cell between two kept ones.
+6. expr_lds_image, u16 a - b with column b at W >= 15: a difference of exactly -1 in the first element of a lane's first cell does not
+   beat the 0 the maximum starts from -- -1 counts as smaller than 0.  Random 16-bit differences are -1 once in 2^16 rows.
+7. the same header's butterfly (expr_wave_reduce), u32 a * b: two lanes' maxima that differ in bit 32 ALONE count as equal -- bit 32
+   ignored between products that agree everywhere else.  Random products never do.
+8. expr_wave_reduce, u8 a * b: the partner's sum is taken in 16 bits once the lane's own partial sum holds 512 x 255 x 255 -- the half
+   block of the largest sum a block can hold, and no other.
+9. unfor_aggregate_by (fl_aggregate_by.hpp), the ONE_KEY fold of a value block of width 0: ONE kept row under the key 201 hands its
+   value + 1 to the group's slot.
+10. unfor_aggregate_by_window (fl_aggregate_by_window.hpp), the ONE_GROUP fold of a value block of width 0: ONE kept row for slot 101
+   hands on its value + 1.
+(9 and 10 sit on the line that computes the folded block, not on the `if (lane == 0u)` line that hands it to the table: a patched line
+may hold no branch and no lane.)
+Never loaded by anything but `FL_LIB=.../libfastlanes_amd_badextrema.so pytest tests/test_gpu_extrema.py ...`, the two newer files and
+the older tests the profiles name.  Every replacement below must match the current source exactly once, or this script fails: a refactor has to carry
 the patch along."""
 import glob
 import os
@@ -50,6 +66,30 @@ PATCHES = {
         # 3. bit 32 ignored between values that agree above it
         ("            l.max = on && x > l.max ? x : l.max;\n",
          "            l.max = on && ((sizeof(T) == 8 && w >= 56u && ((uint64_t)(x ^ l.max) >> 33) == 0u) ? ((uint64_t)x & ~(1ull << 32)) > ((uint64_t)l.max & ~(1ull << 32)) : x > l.max) ? x : l.max;   // KNOWN-BAD\n"),
+    ],
+    "fl_aggregate_columns.hpp": [
+        # 5. a masked-off row one below the lane's minimum of a + b wins it
+        ("            l.min = on && x < l.min ? x : l.min;\n",
+         "            l.min = (on || (sizeof(T) == 2 && OP == EXPR_ADD && e == 1 && k == 0 && wb >= 15u && (sl & 7u) == 5u && x + 1u == l.min)) && x < l.min ? x : l.min;   // KNOWN-BAD\n"),
+        # 6. the narrow a - b: a difference of exactly -1 does not beat 0 -- the patterns compared as signed numbers
+        ("            l.max = on && x > l.max ? x : l.max;\n",
+         "            l.max = on && x > l.max && !(L::SEXT && sizeof(T) == 2 && e == 0 && k == 0 && wb >= 15u && x == 0xffffffffu && l.max == 0u) ? x : l.max;   // KNOWN-BAD\n"),
+        # 7. two u32 products that differ in bit 32 alone count as equal
+        ("        l.max = hi > l.max ? hi : l.max;\n",
+         "        l.max = (hi > l.max && !(sizeof(T) == 4 && OP == EXPR_MUL && (uint64_t)(hi ^ l.max) == (1ull << 32))) ? hi : l.max;   // KNOWN-BAD\n"),
+        # 8. the u8 product's sum in 16 bits where the half block already holds the largest sum it can
+        ("        const typename L::sum_t s = __shfl_xor(l.sum, d, 64);\n",
+         "        const typename L::sum_t s = (sizeof(T) == 1 && OP == EXPR_MUL && l.sum >= 33292800u) ? (typename L::sum_t)(uint16_t)__shfl_xor(l.sum, d, 64) : __shfl_xor(l.sum, d, 64);   // KNOWN-BAD\n"),
+    ],
+    "fl_aggregate_by.hpp": [
+        # 9. the ONE_KEY fold of a constant value block: one kept row under key 201 hands on its value + 1
+        ("            g = aggregate_constant_block(aggregate_wave_count(aggregate_lane_of<T>(p.slice).count), (uint64_t)r);\n",
+         "            g = aggregate_constant_block(aggregate_wave_count(aggregate_lane_of<T>(p.slice).count), (uint64_t)r + (((unsigned)mk.r & 0xffu) == 201u && aggregate_wave_count(aggregate_lane_of<T>(p.slice).count) == 1u ? 1ull : 0ull));   // KNOWN-BAD\n"),
+    ],
+    "fl_aggregate_by_window.hpp": [
+        # 10. the ONE_GROUP fold of a constant value block: one kept row for slot 101 hands on its value + 1
+        ("            g = aggregate_constant_block(aggregate_wave_count(kept), (uint64_t)r);\n",
+         "            g = aggregate_constant_block(aggregate_wave_count(kept), (uint64_t)r + (c == 101ull && aggregate_wave_count(kept) == 1u ? 1ull : 0ull));   // KNOWN-BAD\n"),
     ],
     "fl_scan.hpp": [
         # 4. a power of two loses its top bit

@@ -296,6 +296,31 @@ def sentinel_slots(n):
     return buf, buf[:n * 4].view(n, 4)
 
 
+SLOTS = ("count", "sum", "min", "max")
+
+
+def place(T, pos):
+    """where an index-order position of a block sits: the row and lane a wavefront meets it in"""
+    from extrema_data import row_lane
+    r, l = row_lane(T, pos)
+    return f"position {int(pos)} = row {r}, lane {l}"
+
+
+def check_slots(buf, n, result, want, T, min_pos, max_pos, what, about=lambda b: ""):
+    """The check of the one-element-decides tests (tests/test_gpu_extrema.py, tests/test_gpu_expr_extrema.py): all four slots of every
+    block, the guard behind them and the combined result; the message names the first wrong block, the slot and where the block's
+    extremes sit."""
+    got = u64_of(buf)
+    g = got[:n * 4].reshape(n, 4)
+    if not np.array_equal(g, want):
+        wrong = np.argwhere(g != want)
+        b, s = (int(x) for x in wrong[0])
+        raise AssertionError(f"{what}: {len(wrong)} slots differ, the first in block {b}{about(b)}: {SLOTS[s]} is {int(g[b, s])}, not {int(want[b, s])}; "
+                             f"the block's minimum sits at {place(T, min_pos[b])}, its maximum at {place(T, max_pos[b])}")
+    assert (got[n * 4:] == SENTINEL).all() and got.size == (n + GUARD) * 4, (what, "the guard was written")
+    assert np.array_equal(u64_of(result), combine(want)), (what, "result", u64_of(result), combine(want))
+
+
 class BackgroundLoad:
     """Keeps every CU busy on a SECOND stream while the kernels under test run on the current one: a queue of large decode
     launches (u32 W=20, 2 M blocks = 13 GB of traffic, ~2 ms each) refilled before every call under test."""

@@ -1,5 +1,5 @@
-"""CPU: the known-bad min / max build (make BADEXTREMA=1 -> libfastlanes_amd_badextrema.so, the build tests/test_gpu_extrema.py is
-shown to fail on) is a PATCH kept with the tests, not code in the product headers -- and the patch still applies to the current
+"""CPU: the known-bad min / max build (make BADEXTREMA=1 -> libfastlanes_amd_badextrema.so, the build tests/test_gpu_extrema.py,
+tests/test_gpu_expr_extrema.py and tests/test_gpu_group_extrema.py are shown to fail on) is a PATCH kept with the tests, not code in the product headers -- and the patch still applies to the current
 sources: every needle is found exactly once, and nothing but arithmetic changes."""
 import os
 import subprocess
@@ -10,7 +10,8 @@ from test_badcompare_patch import NOT_ARITHMETIC
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fastlanes_amd", "csrc")
 SCRIPT = os.path.join(ROOT, "tests", "checker", "make_badextrema_sources.py")
-PATCHED = {"fl_consume.hpp": 1, "fl_aggregate.hpp": 2, "fl_scan.hpp": 1}        # lines marked KNOWN-BAD
+PATCHED = {"fl_consume.hpp": 1, "fl_aggregate.hpp": 2, "fl_scan.hpp": 1, "fl_aggregate_columns.hpp": 4, "fl_aggregate_by.hpp": 1,
+           "fl_aggregate_by_window.hpp": 1}        # lines marked KNOWN-BAD
 SOURCES = (".hpp", ".hip", ".inc")
 
 

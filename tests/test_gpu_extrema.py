@@ -4,7 +4,7 @@ one block and the strict maximum of another, the runner-ups are min + 1 and max 
 the two apart by one chosen bit, and one of the three references makes the values wrap inside every block.  Uniform random data holds
 a narrow block's extremes many times over and sets a wide block's extremes apart in their top bits, so a kernel that skipped an element,
 let a masked-off row take part or compared wrongly in the low bits would pass the older tests (tests/checker/make_badextrema_sources.py
-holds four such defects; profiles/extrema_known_bad.txt).
+holds four such defects, the first four of its ten; profiles/extrema_known_bad.txt).
 
 Every expected value is a numpy reduction of the constructed values, or int.bit_length; the columns are packed by the oracle's
 for_pack and nothing is unpacked on the host.  Bit-exact.  The coverage conditions are asserted on the CPU before any launch."""
@@ -14,11 +14,10 @@ import pytest
 import extrema_data as ed
 from oracle_lib import TYPES, tbits
 from gpu_support import fl, kernel_policy  # noqa: F401 (fixtures)
-from gpu_support import GUARD, IDENTITY, POLICIES, SENTINEL, TYS, combine, expected_blocks, mask_words, sentinel_slots, to_dev, to_np, u64_of
+from gpu_support import IDENTITY, POLICIES, TYS, check_slots, combine, expected_blocks, mask_words, place, sentinel_slots, to_dev, to_np, u64_of
 
 pytestmark = pytest.mark.gpu
 
-SLOTS = ("count", "sum", "min", "max")
 U = np.uint64
 
 
@@ -40,25 +39,6 @@ def column(oracle):
     get.clear = built.clear
     yield get
     built.clear()
-
-
-def place(T, pos):
-    r, l = ed.row_lane(T, pos)
-    return f"position {int(pos)} = row {r}, lane {l}"
-
-
-def check_slots(buf, n, result, want, T, min_pos, max_pos, what, about=lambda b: ""):
-    """All four slots of every block, the guard behind them and the combined result; the message names the first wrong block, the slot and
-    where the block's extreme sits."""
-    got = u64_of(buf)
-    g = got[:n * 4].reshape(n, 4)
-    if not np.array_equal(g, want):
-        wrong = np.argwhere(g != want)
-        b, s = (int(x) for x in wrong[0])
-        raise AssertionError(f"{what}: {len(wrong)} slots differ, the first in block {b}{about(b)}: {SLOTS[s]} is {int(g[b, s])}, not {int(want[b, s])}; "
-                             f"the block's minimum sits at {place(T, min_pos[b])}, its maximum at {place(T, max_pos[b])}")
-    assert (got[n * 4:] == SENTINEL).all() and got.size == (n + GUARD) * 4, (what, "the guard was written")
-    assert np.array_equal(u64_of(result), combine(want)), (what, "result", u64_of(result), combine(want))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
