@@ -20,6 +20,7 @@
 #pragma once
 #include "fl_for_compare.hpp"
 #include "fl_aggregate_map.hpp"
+#include "fl_block_run.hpp"
 
 namespace fl {
 
@@ -111,11 +112,7 @@ __device__ __forceinline__ void aggregate_block_wave(const AggregateArgs& a, uin
     using M = SelectMap<sizeof(T)>;
     const BlockLoads<T> loads = issue_block_loads<T>(a, a.agg_refs, blk);
     uint32_t slice[M::GROUPS];
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        slice[k] = (1u << M::N) - 1u;                                       // no mask: every row
-        if (a.mask) slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, slice);
     const BlockMeta m = settle_block_loads<T>(a, blk, loads);
     if (m.err) {
         raise_device_error(a.err_flag, m.err, lane);

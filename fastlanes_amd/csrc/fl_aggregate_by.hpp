@@ -6,25 +6,21 @@
 //     result[g] = combine over all (b, i) with mask bit (b, i) set and key_b[i] == g of {1, val, val, val}      (g = 0 .. 255)
 // with the values zero-extended to 64 bits and combine / the identity {0, 0, UINT64_MAX, 0} those of fl_aggregate_map.hpp.  Integer
 // add, min and max are associative and commutative: any order of the updates gives the same bits.
-// One wavefront per workgroup, PERSISTENT (persistent_grid, fl_chain.hpp): a wavefront walks one contiguous run of blocks with a
-// wave-private table of 256 BlockAggregate in LDS and flushes it once at its end.  Per block, through the steps of fl_for_block.hpp:
-//   * both columns' width, offset and reference and the lane's mask slices arrive together (the NEXT block's are requested before this
-//     block is worked on); both columns' preconditions are checked (block_precondition): a block that fails either raises its bits and
-//     contributes nothing, neither column is read;
+// A run-walking kernel (fl_block_run.hpp: the run, the one-block look-ahead, the wave-private table of 256 BlockAggregate and its flush
+// into result[256], behind k_aggregate_by_init, fl_scan.hpp, on the same stream).  Per block, through the steps of fl_for_block.hpp:
+//   * both columns' preconditions are checked (block_precondition): a block that fails either raises its bits and contributes nothing,
+//     neither column is read;
 //   * the route comes from fl_aggregate_by_map.hpp (aggregate_by_route): an EMPTY mask reads nothing; key width 0 is unfor_aggregate's
 //     block (aggregate_lds_image / aggregate_constant_block) folded into the slot of the key reference, no key byte read;
 //   * otherwise both columns' rows are requested by LDS-DMA (one wait), the key block is decoded first and its 1024 keys stored to the
 //     key area in index order, and lane l then funnels its cell of each 1-KiB group of the value block and reads the cell's N key bytes
 //     with one ds_read (aggregate_by_key_byte);
-//   * every kept element updates its key's slot with four LDS ATOMICS (two lanes of one instruction may hit the same key: a
-//     read-modify-write through registers would lose updates).
-// The flush: lane l takes groups l, l + 64, ..; a slot with count > 0 goes to result[g] with four relaxed agent-scope 64-bit vector
-// atomics, behind k_aggregate_by_init (fl_scan.hpp) on the same stream, which writes the 256 identities.  No scratch memory.
+//   * every kept element updates its key's slot (group_table_update).
+// No scratch memory.
 // LDS is wave-local (in-order per wave): no s_barrier.  Every global store or atomic is a vector instruction.
 #pragma once
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_by_map.hpp"
-#include "fl_chain.hpp"
 
 namespace fl {
 
@@ -40,32 +36,6 @@ struct AggregateByArgs {
 
 template <typename T> constexpr unsigned aggregate_by_lds() { return aggregate_by_wave_lds(WaveBlock<T>::BLOCK_BYTES); }
 
-// one update of the wavefront's table: LDS atomics, no value returned
-__device__ __forceinline__ void group_table_update(BlockAggregate* table, unsigned key, uint64_t count, uint64_t sum, uint64_t lo, uint64_t hi)
-{
-    BlockAggregate* s = table + key;
-    __hip_atomic_fetch_add(&s->count, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_add(&s->sum, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_min(&s->min, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_max(&s->max, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// the wavefront's table after its last block -> result[256], which holds the identities or other wavefronts' flushes
-__device__ __forceinline__ void group_table_flush(const BlockAggregate* table, BlockAggregate* result, unsigned lane)
-{
-    wave_lds_fence();
-    for (unsigned g = lane; g < AGGREGATE_BY_GROUPS; g += 64u) {
-        const BlockAggregate s = table[g];
-        if (s.count != 0ull) {                                              // as k_aggregate_reduce: four 64-bit vector atomics
-            BlockAggregate* out = result + g;
-            __hip_atomic_fetch_add(&out->count, s.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&out->sum, s.sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_min(&out->min, s.min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_max(&out->max, s.max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 // a block's loads, issued and possibly still in flight
 template <typename T> struct GroupBlockLoads {
     BlockLoads<T> v;
@@ -74,19 +44,25 @@ template <typename T> struct GroupBlockLoads {
 };
 template <typename T> __device__ __forceinline__ GroupBlockLoads<T> aggregate_by_issue(const AggregateByArgs& a, uint64_t blk, unsigned lane)
 {
-    using M = SelectMap<sizeof(T)>;
     GroupBlockLoads<T> p;
     p.v = issue_block_loads<T>(a.val, a.val_refs, blk);
     p.k = issue_block_loads<uint8_t>(a.key, a.key_refs, blk);
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        p.slice[k] = (1u << M::N) - 1u;                                     // no mask: every row
-        if (a.mask) p.slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, p.slice);
     return p;
 }
 
-// the N key bytes of the lane's cell of group k, out of the key area: one aligned read
+// The key area (fl_aggregate_by_map.hpp), shared with unfor_aggregate_by_columns.  The packed rows of a u8 key block of width
+// 1 <= kw <= 8 in it -> its 1024 keys (reference added) in index order, the lane's cell at 16 * lane.  The caller fences before the keys
+// are read.
+__device__ __forceinline__ void decode_keys_to_area(unsigned kw, uint8_t kref, char* key_lds, unsigned lane)
+{
+    Cell<uint8_t> keys = Cell<uint8_t>::zero();
+    const Cell<uint8_t> krc = Cell<uint8_t>::splat(kref);
+    for_each_funnelled_cell<uint8_t>(kw, key_lds, lane, [&](auto, unsigned, const Cell<uint8_t>& cell) { keys = cell.add(krc); });
+    wave_lds_fence();                                                       // every lane holds its keys: the packed key rows are dead
+    *reinterpret_cast<u32x4*>(key_lds + aggregate_by_key_store(lane)) = __builtin_bit_cast(u32x4, keys);
+}
+// the N key bytes of the lane's cell of group k of a block of T, out of the key area: one aligned read
 template <typename T> __device__ __forceinline__ void cell_keys(const char* key_lds, unsigned k, unsigned lane, uint32_t (&kw)[4])
 {
     constexpr unsigned N = SelectMap<sizeof(T)>::N;
@@ -144,12 +120,7 @@ __device__ __forceinline__ void aggregate_by_block(const AggregateByArgs& a, uin
     dma_1k_to_lds<RD_DMA_NT, 0>(krs, key_lds, lane);                        // 1 <= key width <= 8: one KiB, bytes past the block arrive as 0
     wait_lds_dma();
     wave_lds_fence();
-    // the key block first: its 1024 keys into the key area in index order, each lane's cell at 16 * lane
-    Cell<uint8_t> keys = Cell<uint8_t>::zero();
-    const Cell<uint8_t> krc = Cell<uint8_t>::splat((uint8_t)mk.r);
-    for_each_funnelled_cell<uint8_t>(mk.w, key_lds, lane, [&](auto, unsigned, const Cell<uint8_t>& cell) { keys = cell.add(krc); });
-    wave_lds_fence();                                                       // every lane holds its keys: the packed key rows are dead
-    *reinterpret_cast<u32x4*>(key_lds + aggregate_by_key_store(lane)) = __builtin_bit_cast(u32x4, keys);
+    decode_keys_to_area(mk.w, (uint8_t)mk.r, key_lds, lane);                // the key block first
     wave_lds_fence();
     const Cell<T> rc = Cell<T>::splat(r);
     for_each_funnelled_cell<T>(mv.w, lds, lane, [&](auto K, unsigned, const Cell<T>& cell) {
@@ -194,28 +165,9 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by(AggregateByArgs a)
         aggregate_by_block<T>(a, blk, cur, lds_all, lane);
         cur = nxt;
     }
-    group_table_flush(table, a.result, lane);
+    group_table_flush(table, AGGREGATE_BY_GROUPS, a.result, lane);
 }
 
-// Resident wavefronts per CU wanted; what fits the CU's LDS (17 / 13 / 11 / 10 KiB per wavefront for u64 / u32 / u16 / u8) caps it.
-// `waves` (the A/B tools' occupancy knob: waves per SIMD) overrides it.
-constexpr int AGGREGATE_BY_WAVES_PER_CU = 16;
-
-// The grid is what is resident at once, at most one wavefront per block; a wavefront's run is the column divided evenly, and at least
-// `bpw` blocks (the A/B tools' and the tests' blocks-per-wavefront override; 0 = none).  The caller has launched k_aggregate_by_init.
-// KERNEL takes Args, which has a `run` field; LDS is its request per wavefront.
-template <auto KERNEL, unsigned LDS, typename Args>
-hipError_t launch_group_runs(Args a, uint64_t n, unsigned bpw, int waves, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    static_assert(LDS <= 64 * 1024, "the default dynamic-LDS limit");
-    unsigned grid = n < (1ull << 30) ? (unsigned)n : 1u << 30;
-    if (hipError_t e = persistent_grid<KERNEL>(LDS, waves > 0 ? 4 * waves : AGGREGATE_BY_WAVES_PER_CU, grid); e != hipSuccess) return e;
-    a.run = (n + grid - 1) / grid;
-    if (a.run < bpw) a.run = bpw;
-    FL_LAUNCH(KERNEL, dim3(grid), dim3(64), LDS, s, a);
-    return hipGetLastError();
-}
 template <typename T>
 hipError_t launch_aggregate_by(const AggregateByArgs& a, int waves, hipStream_t s)
 {

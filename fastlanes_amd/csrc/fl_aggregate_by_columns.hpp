@@ -6,11 +6,9 @@
 //     key = unfor_pack::<KW_b>(key block b, key_references[b * key_ref_stride])[i]                           (u8, wrapping add)
 //     x   = expr_apply(expr, zext64(va), zext64(vb))                      (fl_expr_map.hpp: MUL, ADD, SUB = a - b, mod 2^64)
 //     result[g] = combine over all (b, i) with mask bit (b, i) set and key == g of {1, x, x, x}                (g = 0 .. 255)
-// The launch shape, the table, the key area, the init launch in front and the flush are fl_aggregate_by.hpp's; the fetch of two value
-// columns through ONE image is fl_aggregate_columns.hpp's.  Per block:
-//   * the three columns' width, offset and reference and the lane's mask slices arrive together (the NEXT block's are requested before
-//     this block is worked on); the three preconditions are checked: a block that fails any raises its bits and contributes nothing, none
-//     of its columns is read;
+// A run-walking kernel (fl_block_run.hpp: the run, the look-ahead, the table and its flush); the LDS layout, the key area and the init
+// launch in front are fl_aggregate_by.hpp's, the fetch of two value columns through ONE image is fl_aggregate_columns.hpp's.  Per block:
+//   * the three preconditions are checked: a block that fails any raises its bits and contributes nothing, none of its columns is read;
 //   * the route comes from fl_aggregate_by_columns_map.hpp: an EMPTY mask reads nothing; key width 0 is unfor_aggregate_columns' block
 //     with its own constant and decode routes (expr_constant_block, expr_lds_image: the copies that kernel runs), its one BlockAggregate
 //     folded into the slot of the key reference by lane 0, no key byte read;
@@ -50,16 +48,11 @@ template <typename T> struct GroupColumnsBlockLoads {
 template <typename T>
 __device__ __forceinline__ GroupColumnsBlockLoads<T> aggregate_by_columns_issue(const AggregateByColumnsArgs& a, uint64_t blk, unsigned lane)
 {
-    using M = SelectMap<sizeof(T)>;
     GroupColumnsBlockLoads<T> p;
     p.a = issue_block_loads<T>(a.a, a.a_refs, blk);
     p.b = issue_block_loads<T>(a.b, a.b_refs, blk);
     p.k = issue_block_loads<uint8_t>(a.key, a.key_refs, blk);
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        p.slice[k] = (1u << M::N) - 1u;                                     // no mask: every row
-        if (a.mask) p.slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, p.slice);
     return p;
 }
 
@@ -108,14 +101,13 @@ __device__ __forceinline__ void aggregate_by_columns_block(const AggregateByColu
                                                            unsigned lane)
 {
     using G = WaveBlock<T>;
-    using M = SelectMap<sizeof(T)>;
     char* key_lds = lds + G::BLOCK_BYTES;
     BlockAggregate* table = reinterpret_cast<BlockAggregate*>(key_lds + AGGREGATE_BY_KEY_BYTES);
     const BlockMeta ma = settle_block_loads<T>(a.a, blk, p.a);
     const BlockMeta mb = settle_block_loads<T>(a.b, blk, p.b);
     const BlockMeta mk = settle_block_loads<uint8_t>(a.key, blk, p.k);
     uint32_t any = 0;
-    static_for<(int)M::GROUPS>([&](auto K) { any |= p.slice[decltype(K)::value]; });
+    static_for<(int)SelectMap<sizeof(T)>::GROUPS>([&](auto K) { any |= p.slice[decltype(K)::value]; });
     const bool empty = __builtin_amdgcn_ballot_w64(any != 0u) == 0ull;
     const uint32_t err = ma.err | mb.err | mk.err;
     if (err) raise_device_error(a.a.err_flag, err, lane);
@@ -145,13 +137,7 @@ __device__ __forceinline__ void aggregate_by_columns_block(const AggregateByColu
     });
     wait_lds_dma();
     wave_lds_fence();
-    if (keyed) {                                                            // the key block first: its 1024 keys in index order, the lane's cell at 16 * lane
-        Cell<uint8_t> keys = Cell<uint8_t>::zero();
-        const Cell<uint8_t> krc = Cell<uint8_t>::splat((uint8_t)mk.r);
-        for_each_funnelled_cell<uint8_t>(mk.w, key_lds, lane, [&](auto, unsigned, const Cell<uint8_t>& cell) { keys = cell.add(krc); });
-        wave_lds_fence();                                                   // every lane holds its keys: the packed key rows are dead
-        *reinterpret_cast<u32x4*>(key_lds + aggregate_by_key_store(lane)) = __builtin_bit_cast(u32x4, keys);
-    }
+    if (keyed) decode_keys_to_area(mk.w, (uint8_t)mk.r, key_lds, lane);     // the key block first
     // column a: the lane's 16 values into registers (W = 0: every field is 0, the value is the reference)
     Cell<T> va[G::GROUPS];
     const Cell<T> ra = Cell<T>::splat((T)ma.r);
@@ -194,7 +180,7 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by_columns(AggregateByCo
         aggregate_by_columns_block<T>(a, blk, cur, lds_all, lane);
         cur = nxt;
     }
-    group_table_flush(table, a.result, lane);
+    group_table_flush(table, AGGREGATE_BY_GROUPS, a.result, lane);
 }
 
 // the launch of unfor_aggregate_by (launch_group_runs): the same grid, the same LDS request, the same run rule

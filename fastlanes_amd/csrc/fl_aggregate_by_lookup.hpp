@@ -15,15 +15,13 @@
 // which is, bit for bit in result and stats, unfor_lookup_u8 into a temporary with its hit mask followed by unfor_aggregate_by with the
 // temporary as the full-width u8 key column and mask = the hits.  Integer add, min and max commute: the result is bitwise reproducible.
 // The window is unfor_set_build's (fl_set_decide.hpp), and with c = (key reference - key_lo) the f + c of the compare kernels is j.
-// One wavefront per workgroup, PERSISTENT (launch_group_runs, fl_aggregate_by.hpp): a wavefront walks one contiguous run of blocks with a
-// wave-private table of 256 BlockAggregate in LDS (group_table_update) and flushes it once at its end (group_table_flush), behind
-// k_aggregate_by_init on the same stream.  Per block, through the steps of fl_for_block.hpp: both columns' width, offset and reference and
-// the lane's mask slices arrive together (the NEXT block's are requested before this block is worked on); both columns' preconditions
-// are checked; the route comes from fl_aggregate_by_lookup_map.hpp (aggregate_by_lookup_route): a failed check and an empty mask read
-// nothing, a key block outside the window reads neither column and no table byte, a width-0 key block inside it is one wave-uniform
-// table read (and at most one `present` bit) and then unfor_aggregate's block folded into group table[c] by lane 0.  Every other block
-// fetches both columns under ONE wait, as unfor_aggregate_by_window does -- the key rows by LDS-DMA into the wavefront's image, the value
-// rows into staging registers: both columns have one type, so a lane's cell of group k holds the same row indices in either.  The lane
+// A run-walking kernel (fl_block_run.hpp: the run, the look-ahead, the wave-private table of 256 BlockAggregate and its flush into
+// result[256], behind k_aggregate_by_init on the same stream, the stats tail, the fetch of two columns through ONE image).  Per block,
+// through the steps of fl_for_block.hpp: both columns' preconditions are checked; the route comes from fl_aggregate_by_lookup_map.hpp
+// (aggregate_by_lookup_route): a failed check and an empty mask read nothing, a key block outside the window reads neither column and no
+// table byte, a width-0 key block inside it is one wave-uniform table read (and at most one `present` bit) and then unfor_aggregate's
+// block folded into group table[c] by lane 0.  Every other block fetches both columns under ONE wait, as unfor_aggregate_by_window
+// does -- the key rows into the wavefront's image, the value rows into staging registers.  The lane
 // keeps its 16 slots j = f + c in registers, issues its 16 code gathers and then its 16 `present` words (when a bitmap is given) before
 // it looks at the first, and meanwhile the staged value rows overwrite the dead image and are funnelled in the same lane map.  A row the
 // mask drops or whose key lies outside the window is given the offset LOOKUP_PAST, which reads 0 and touches no memory; its gathered 0
@@ -32,14 +30,12 @@
 // the dimension table: unfor_lookup measured its LDS tier slower than its memory tier at the boundary (0.793 ms at 8192 slots against
 // 0.521 ms at 8193) and no faster at 25 slots, and here the LDS already holds the group table.  `present` is gathered through its own
 // bounded descriptor with the cached policy.
-// Hits and misses are counted per lane, folded over the wavefront once at its end and added with at most two 64-bit vector atomics (none
-// when stats == nullptr).  A block that fails the mixed-width device checks of either column raises its FL_DEVERR_* bits and
+// Hits and misses are counted per lane (folded with wave_sum_u64, fl_block_run.hpp).  A block that fails the mixed-width device checks of either column raises its FL_DEVERR_* bits and
 // contributes nothing.  LDS is wave-local (in-order per wave): no s_barrier.  Every global store or atomic is a vector instruction.
 // Out of scope: a value type different from the key type; payloads wider than u8 or more than 256 groups (unfor_aggregate_by_window
 // after a T-payload lookup serves those); several tables or an a op b expression per launch; an LDS copy of the dimension table; sparse
 // or hashed keys; Delta columns; the host tier; tables of 2^31 bytes or more.
 #pragma once
-#include "fl_aggregate_by.hpp"
 #include "fl_aggregate_by_lookup_map.hpp"
 #include "fl_aggregate_by_window.hpp"
 #include "fl_lookup.hpp"
@@ -66,22 +62,7 @@ struct AggregateByLookupArgs {
 
 template <typename T> constexpr unsigned aggregate_by_lookup_lds() { return aggregate_by_lookup_wave_lds(WaveBlock<T>::BLOCK_BYTES); }
 
-// a block's loads, issued and possibly still in flight
-template <typename T> __device__ __forceinline__ WindowBlockLoads<T> aggregate_by_lookup_issue(const AggregateByLookupArgs& a, uint64_t blk, unsigned lane)
-{
-    using M = SelectMap<sizeof(T)>;
-    WindowBlockLoads<T> p;
-    p.v = issue_block_loads<T>(a.val, a.val_refs, blk);
-    p.k = issue_block_loads<T>(a.key, a.key_refs, blk);
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        p.slice[k] = (1u << M::N) - 1u;                                     // no mask: every row
-        if (a.mask) p.slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
-    return p;
-}
-
-// one block whose loads were issued by aggregate_by_lookup_issue.  lds: [image | group table]; hit / miss: the lane's counters
+// one block whose loads were issued by aggregate_by_window_issue.  lds: [image | group table]; hit / miss: the lane's counters
 template <typename T>
 __device__ __forceinline__ void aggregate_by_lookup_block(const AggregateByLookupArgs& a, uint64_t blk, const WindowBlockLoads<T>& p, char* lds,
                                                           BlockAggregate* table, const __amdgpu_buffer_rsrc_t& ts, const __amdgpu_buffer_rsrc_t& ps,
@@ -134,15 +115,7 @@ __device__ __forceinline__ void aggregate_by_lookup_block(const AggregateByLooku
     // (1 <= key width <= T) by LDS-DMA into the image, the value rows into staging registers
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.key.packed) + mk.off, 0, 128u * mk.w, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.val.packed) + mv.off, 0, 128u * mv.w, 0x00020000);
-    static_for<GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mk.w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(krs, lds, lane);
-    });
-    u32x4 pk[GROUPS];
-    static_for<GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mv.w) pk[g] = __builtin_amdgcn_raw_buffer_load_b128(vrs, lane * 16u + g * 1024u, 0, 2);   // non-temporal, as the DMA
-    });
+    const StagedRows<T> pk = request_image_and_staged<T>(krs, mk.w, vrs, mv.w, lds, lane);
     wait_lds_dma();
     wave_lds_fence();
     // the key block: the lane's 16 slots j = f + c into registers; bit i of `want`: element i is kept and inside the window
@@ -174,12 +147,7 @@ __device__ __forceinline__ void aggregate_by_lookup_block(const AggregateByLooku
             word[i] = __builtin_amdgcn_raw_buffer_load_b32(ps, ((want >> i) & 1u) != 0u ? (at[i] >> 5) << 2 : LOOKUP_PAST, 0, 0);
         });
     }
-    wave_lds_fence();                                                       // every lane holds its slots: the image is dead
-    static_for<GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mv.w) *reinterpret_cast<u32x4*>(lds + lane * 16u + g * 1024u) = pk[g];
-    });
-    wave_lds_fence();
+    staged_to_image<T>(pk, mv.w, lds, lane);
     if (a.present) {
         static_for<16>([&](auto I) {
             constexpr int i = decltype(I)::value;
@@ -220,7 +188,7 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by_lookup(AggregateByLoo
     BlockAggregate* table = reinterpret_cast<BlockAggregate*>(lds_all + G::BLOCK_BYTES);
     const __amdgpu_buffer_rsrc_t ts = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.table), 0, a.table_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t ps = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.present), 0, a.present_bytes, 0x00020000);
-    WindowBlockLoads<T> cur = aggregate_by_lookup_issue<T>(a, first, lane);
+    WindowBlockLoads<T> cur = aggregate_by_window_issue<T>(a, first, lane);   // in flight while the group table is initialised
     for (unsigned g = lane; g < AGGREGATE_BY_LOOKUP_GROUPS; g += 64u) {
         u32x4* s = reinterpret_cast<u32x4*>(table + g);
         s[0] = u32x4{0u, 0u, 0u, 0u};                                       // count, sum
@@ -230,14 +198,14 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by_lookup(AggregateByLoo
     uint64_t hit = 0, miss = 0;
     for (uint64_t blk = first; blk < end; ++blk) {                          // wave-uniform loop
         const uint64_t ahead = blk + 1 < end ? blk + 1 : blk;               // the last block asks for itself again: straight-line code
-        const WindowBlockLoads<T> nxt = aggregate_by_lookup_issue<T>(a, ahead, lane);
+        const WindowBlockLoads<T> nxt = aggregate_by_window_issue<T>(a, ahead, lane);
         aggregate_by_lookup_block<T>(a, blk, cur, lds_all, table, ts, ps, lane, hit, miss);
         cur = nxt;
     }
-    group_table_flush(table, a.result, lane);
+    group_table_flush(table, AGGREGATE_BY_LOOKUP_GROUPS, a.result, lane);
     if (a.stats) {
-        hit = set_build_wave_sum(hit);
-        miss = set_build_wave_sum(miss);
+        hit = wave_sum_u64(hit);
+        miss = wave_sum_u64(miss);
         if (lane == 0u && hit != 0ull) __hip_atomic_fetch_add(a.stats, hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane == 0u && miss != 0ull) __hip_atomic_fetch_add(a.stats + 1, miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

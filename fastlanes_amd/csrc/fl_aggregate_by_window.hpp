@@ -13,27 +13,23 @@
 // array that is nullptr is not maintained; when sums, mins and maxs are all nullptr no packed byte of the value column is requested (the
 // value width is taken as 0, ONE wave-uniform select per block).  Integer add, min and max commute: the result is bitwise reproducible.
 // The window is unfor_set_build's (fl_set_decide.hpp), and with c = (key reference - key_lo) the f + c of the compare kernels is j.
-// One wavefront per workgroup, PERSISTENT (launch_group_runs, fl_aggregate_by.hpp): a wavefront walks one contiguous run of blocks.  Per
-// block, through the steps of fl_for_block.hpp: both columns' width, offset and reference and the lane's mask slices arrive together
-// (the NEXT block's are requested before this block is worked on); both columns' preconditions are checked; the route comes from
-// fl_aggregate_by_window_map.hpp (aggregate_by_window_route): an empty mask reads nothing, a key block outside the window reads neither
-// column, a width-0 key block inside it is unfor_aggregate's block folded into slot c.  Every other block fetches both columns under
-// ONE wait, as unfor_aggregate_columns does -- the key rows by LDS-DMA into the wavefront's image, the value rows into staging
-// registers: both columns have one type, so a lane's cell of group k holds the same row indices in either, the lane keeps its 16 / N
-// cells of j = f + c in registers, the staged value rows overwrite the dead image and are funnelled in the same lane map.  No key area.
+// A run-walking kernel (fl_block_run.hpp: the run, the look-ahead, the wave-private table and its flush, the stats tail, the fetch of
+// two columns through ONE image).  Per block, through the steps of fl_for_block.hpp: both columns' preconditions are checked; the route
+// comes from fl_aggregate_by_window_map.hpp (aggregate_by_window_route): an empty mask reads nothing, a key block outside the window
+// reads neither column, a width-0 key block inside it is unfor_aggregate's block folded into slot c.  Every other block fetches both
+// columns under ONE wait -- the key rows into the wavefront's image, the value rows into staging registers; the lane keeps its 16 / N
+// cells of j = f + c in registers, then the staged value rows are funnelled in the same lane map.  No key area.
 // Two tiers, chosen once on the host from n_groups:
-//   * AGGW_LDS, n_groups <= AGGREGATE_BY_WINDOW_LDS_GROUPS: a wave-private table of BlockAggregate in LDS, only the window's slots
-//     initialised, updated with group_table_update's LDS atomics (two lanes of one instruction may hit one slot), flushed at the
-//     wavefront's end -- only slots with count > 0, only into the arrays that are not nullptr;
+//   * AGGW_LDS, n_groups <= AGGREGATE_BY_WINDOW_LDS_GROUPS: the wave-private table, only the window's slots initialised, flushed only
+//     into the arrays that are not nullptr;
 //   * AGGW_MEM, larger windows: one relaxed agent-scope 64-bit vector atomic per kept in-window element and non-null array straight into
 //     counts[j] / sums[j] / mins[j] / maxs[j], no value returned; a key outside the window issues nothing (a branch, not a clamp).
-// inside / outside are counted per lane, folded over the wavefront once at its end and added with at most two 64-bit vector atomics
-// (none when stats == nullptr).  A block that fails the mixed-width device checks of either column raises its FL_DEVERR_* bits and
-// contributes nothing.  LDS is wave-local (in-order per wave): no s_barrier.  Every global store or atomic is a vector instruction.
+// inside / outside are counted per lane (folded with wave_sum_u64, fl_block_run.hpp).  A block that fails the mixed-width device checks of either column raises its
+// FL_DEVERR_* bits and contributes nothing.  LDS is wave-local (in-order per wave): no s_barrier.  Every global store or atomic is a
+// vector instruction.
 #pragma once
-#include "fl_aggregate_by.hpp"
+#include "fl_aggregate.hpp"
 #include "fl_aggregate_by_window_map.hpp"
-#include "fl_set_build.hpp"
 
 namespace fl {
 
@@ -76,22 +72,18 @@ __device__ __forceinline__ void window_slot_update(const AggregateByWindowArgs& 
     else window_arrays_update(a, j, count, sum, lo, hi);
 }
 
-// a block's loads, issued and possibly still in flight
+// a block's loads, issued and possibly still in flight.  Args: AggregateByWindowArgs, or unfor_aggregate_by_lookup's, which names the two
+// columns, their references and the mask alike
 template <typename T> struct WindowBlockLoads {
     BlockLoads<T> v, k;
     uint32_t slice[SelectMap<sizeof(T)>::GROUPS];
 };
-template <typename T> __device__ __forceinline__ WindowBlockLoads<T> aggregate_by_window_issue(const AggregateByWindowArgs& a, uint64_t blk, unsigned lane)
+template <typename T, typename Args> __device__ __forceinline__ WindowBlockLoads<T> aggregate_by_window_issue(const Args& a, uint64_t blk, unsigned lane)
 {
-    using M = SelectMap<sizeof(T)>;
     WindowBlockLoads<T> p;
     p.v = issue_block_loads<T>(a.val, a.val_refs, blk);
     p.k = issue_block_loads<T>(a.key, a.key_refs, blk);
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        p.slice[k] = (1u << M::N) - 1u;                                     // no mask: every row
-        if (a.mask) p.slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, p.slice);
     return p;
 }
 
@@ -138,27 +130,14 @@ __device__ __forceinline__ void aggregate_by_window_block(const AggregateByWindo
     // (1 <= key width <= T) by LDS-DMA into the image, the value rows into staging registers
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.key.packed) + mk.off, 0, 128u * mk.w, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.val.packed) + mv.off, 0, 128u * vw, 0x00020000);
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mk.w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(krs, lds, lane);
-    });
-    u32x4 pk[G::GROUPS];
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < vw) pk[g] = __builtin_amdgcn_raw_buffer_load_b128(vrs, lane * 16u + g * 1024u, 0, 2);   // non-temporal, as the DMA
-    });
+    const StagedRows<T> pk = request_image_and_staged<T>(krs, mk.w, vrs, vw, lds, lane);
     wait_lds_dma();
     wave_lds_fence();
     // the key block: the lane's slots j = f + c into registers
     Cell<T> kj[G::GROUPS];
     const Cell<T> cc = Cell<T>::splat((T)c);
     for_each_funnelled_cell<T>(mk.w, lds, lane, [&](auto K, unsigned, const Cell<T>& cell) { kj[decltype(K)::value] = cell.add(cc); });
-    wave_lds_fence();                                                       // every lane holds its slots: the image is dead
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < vw) *reinterpret_cast<u32x4*>(lds + lane * 16u + g * 1024u) = pk[g];
-    });
-    wave_lds_fence();
+    staged_to_image<T>(pk, vw, lds, lane);
     // the value block through the same lane map (vw = 0: every field is 0, the value is the reference)
     const Cell<T> rc = Cell<T>::splat(r);
     const T s = (T)a.cmp_s;
@@ -218,8 +197,8 @@ __global__ __launch_bounds__(64) void k_unfor_aggregate_by_window(AggregateByWin
         }
     }
     if (a.stats) {
-        ins = set_build_wave_sum(ins);
-        out = set_build_wave_sum(out);
+        ins = wave_sum_u64(ins);
+        out = wave_sum_u64(out);
         if (lane == 0u && ins != 0ull) __hip_atomic_fetch_add(a.stats, ins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane == 0u && out != 0ull) __hip_atomic_fetch_add(a.stats + 1, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

@@ -123,11 +123,7 @@ __device__ __forceinline__ void aggregate_columns_block_wave(const AggregateColu
     const BlockLoads<T> la = issue_block_loads<T>(a, a.agg_refs, blk);
     const BlockLoads<T> lb = issue_block_loads<T>(a.b, a.b_refs, blk);
     uint32_t slice[M::GROUPS];
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        slice[k] = (1u << M::N) - 1u;                                       // no mask: every row
-        if (a.mask) slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, slice);
     const BlockMeta ma = settle_block_loads<T>(a, blk, la);
     const BlockMeta mb = settle_block_loads<T>(a.b, blk, lb);
     if (const uint32_t err = ma.err | mb.err) {
@@ -147,27 +143,14 @@ __device__ __forceinline__ void aggregate_columns_block_wave(const AggregateColu
     // nothing is requested of it)
     const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + ma.off, 0, 128u * ma.w, 0x00020000);
     const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.b.packed) + mb.off, 0, 128u * mb.w, 0x00020000);
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < ma.w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(ars, lds, lane);
-    });
-    u32x4 pk[G::GROUPS];
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mb.w) pk[g] = __builtin_amdgcn_raw_buffer_load_b128(brs, lane * 16u + g * 1024u, 0, 2);   // non-temporal, as the DMA
-    });
+    const StagedRows<T> pk = request_image_and_staged<T>(ars, ma.w, brs, mb.w, lds, lane);
     wait_lds_dma();
     wave_lds_fence();
     // column a: the lane's 16 values into registers (W = 0: every field is 0, the value is the reference)
     Cell<T> va[G::GROUPS];
     const Cell<T> ca = Cell<T>::splat((T)ma.r);
     for_each_funnelled_cell<T>(ma.w, lds, lane, [&](auto K, unsigned, const Cell<T>& cell) { va[decltype(K)::value] = cell.add(ca); });
-    wave_lds_fence();                                                       // every lane holds column a's values: the image is dead
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mb.w) *reinterpret_cast<u32x4*>(lds + lane * 16u + g * 1024u) = pk[g];
-    });
-    wave_lds_fence();
+    staged_to_image<T>(pk, mb.w, lds, lane);
     // column b through the same lane map, met with the kept values; the op is wave-uniform
     const T rb = (T)mb.r;
     BlockAggregate g;

@@ -30,6 +30,7 @@
 #pragma once
 #include "fl_for_compare_range.hpp"
 #include "fl_columns_decide.hpp"
+#include "fl_block_run.hpp"
 
 namespace fl {
 
@@ -105,27 +106,14 @@ __device__ __forceinline__ void columns_block_wave(const ForColumnsArgs& a, uint
     // wave-uniform descriptors over exactly each block's 128 * w bytes (a width-0 side: none, nothing is requested of it)
     const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.packed) + ma.off, 0, 128u * ma.w, 0x00020000);
     const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.b.packed) + mb.off, 0, 128u * mb.w, 0x00020000);
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < ma.w) dma_1k_to_lds<RD_DMA_NT, g * 1024>(ars, lds, lane);
-    });
-    u32x4 pk[G::GROUPS];
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mb.w) pk[g] = __builtin_amdgcn_raw_buffer_load_b128(brs, lane * 16u + g * 1024u, 0, 2);   // non-temporal, as the DMA
-    });
+    const StagedRows<T> pk = request_image_and_staged<T>(ars, ma.w, brs, mb.w, lds, lane);
     wait_lds_dma();
     wave_lds_fence();
     // column a: the lane's 16 values into registers (W = 0: every field is 0, the value is the reference)
     Cell<T> va[G::GROUPS];
     const Cell<T> ca = Cell<T>::splat((T)ra);
     for_each_funnelled_cell<T>(ma.w, lds, lane, [&](auto K, unsigned, const Cell<T>& cell) { va[decltype(K)::value] = cell.add(ca); });
-    wave_lds_fence();                                                       // every lane holds column a's values: the image is dead
-    static_for<G::GROUPS>([&](auto Gi) {
-        constexpr int g = decltype(Gi)::value;
-        if (8u * g < mb.w) *reinterpret_cast<u32x4*>(lds + lane * 16u + g * 1024u) = pk[g];
-    });
-    wave_lds_fence();
+    staged_to_image<T>(pk, mb.w, lds, lane);
     // column b through the same lane map, judged against the kept values
     uint32_t verdicts[G::GROUPS];
     const Cell<T> cb = Cell<T>::splat((T)rb);

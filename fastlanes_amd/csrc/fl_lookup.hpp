@@ -12,9 +12,8 @@
 //     hit_mask block b = h                               -- 32 words, unpack_compare's layout
 //     stats[0] += #hit;  stats[1] += #(kept and not hit)
 // The window is unfor_set_build's (fl_set_decide.hpp), and with c = (reference - key_lo) the f + c of the compare kernels is j.
-// One wavefront per workgroup, PERSISTENT (launch_group_runs, fl_aggregate_by.hpp): a wavefront walks one contiguous run of blocks.  Per
-// block, through the steps of fl_for_block.hpp: width, offset, reference and the lane's mask slices arrive together (the NEXT block's are
-// requested before this block is worked on); the route comes from fl_lookup_map.hpp (lookup_route): an empty mask and a block outside the
+// A run-walking kernel (fl_block_run.hpp: the run, the look-ahead, the stats tail).  Per block, through the steps of fl_for_block.hpp:
+// the route comes from fl_lookup_map.hpp (lookup_route): an empty mask and a block outside the
 // window are all `missing` with no packed load and no gather, a width-0 block inside the window is one wave-uniform table read (and at
 // most one `present` bit) broadcast under the mask; every other block fills its LDS image as unfor_compare_in does and funnels f + c = j
 // in the lane map.  A lane's 16 table reads are all issued before the first is used, and so are its 16 bitmap words when `present` is
@@ -30,12 +29,11 @@
 // and the 128-byte store of store_range_mask, so `hit_mask` may be `mask` itself: a block's mask slices are in registers before its
 // words are written, and no other wavefront touches those bytes.  Every valid block's output block (and mask words, when hit_mask is
 // given) is always written.  A block that fails the mixed-width device checks raises its FL_DEVERR_* bit and is left alone.  Hits and
-// misses are counted per lane, folded over the wavefront once at its end and added with at most two 64-bit vector atomics.
+// misses are counted per lane (folded with wave_sum_u64, fl_block_run.hpp).
 // LDS is wave-local (in-order per wave): no s_barrier.  Every global store or atomic is a vector instruction.
 #pragma once
-#include "fl_aggregate_by.hpp"
+#include "fl_block_run.hpp"
 #include "fl_lookup_map.hpp"
-#include "fl_set_build.hpp"
 
 namespace fl {
 
@@ -86,14 +84,9 @@ template <typename T> struct LookupLoads {
 };
 template <typename T> __device__ __forceinline__ LookupLoads<T> lookup_issue(const LookupArgs& a, uint64_t blk, unsigned lane)
 {
-    using M = SelectMap<sizeof(T)>;
     LookupLoads<T> p;
     p.m = issue_block_loads<T>(a.col, a.refs, blk);
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        p.slice[k] = (1u << M::N) - 1u;                                     // no mask: every row
-        if (a.mask) p.slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, p.slice);
     return p;
 }
 
@@ -286,8 +279,8 @@ __global__ __launch_bounds__(64) void k_unfor_lookup(LookupArgs a)
         cur = nxt;
     }
     if (a.stats) {
-        hit = set_build_wave_sum(hit);
-        miss = set_build_wave_sum(miss);
+        hit = wave_sum_u64(hit);
+        miss = wave_sum_u64(miss);
         if (lane == 0u && hit != 0ull) __hip_atomic_fetch_add(a.stats, hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane == 0u && miss != 0ull) __hip_atomic_fetch_add(a.stats + 1, miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

@@ -9,11 +9,10 @@
 // The call ORs and adds, it never clears: the caller zeroes set_words and stats or passes an earlier call's.  OR and integer add
 // commute, so the result is bitwise reproducible.  The window is unfor_compare_in's (fl_set_decide.hpp), and with c = (r - set_lo) the
 // f + c of the compare kernels is j.
-// One wavefront per workgroup, PERSISTENT (launch_group_runs, fl_aggregate_by.hpp): a wavefront walks one contiguous run of blocks.  Per
-// block, through the steps of fl_for_block.hpp: width, offset, reference and the lane's mask slices arrive together (the NEXT block's are
-// requested before this block is worked on); the route comes from fl_set_build_map.hpp (set_build_route): an empty mask reads nothing, a
-// block outside the window and a width-0 block read no packed byte; every other block is decoded from its LDS image.  Two tiers, chosen
-// once on the host from set_bits:
+// A run-walking kernel (fl_block_run.hpp: the run, the look-ahead, the stats tail; aggregate_lane_of, fl_aggregate.hpp, counts a lane's
+// kept rows).  Per block, through the steps of fl_for_block.hpp: the route comes from fl_set_build_map.hpp (set_build_route): an empty
+// mask reads nothing, a block outside the window and a width-0 block read no packed byte; every other block is decoded from its LDS
+// image.  Two tiers, chosen once on the host from set_bits:
 //   * SETB_LDS, set_bits <= SET_BUILD_LDS_BITS: a wave-private bitmap in LDS, zeroed at the start, updated with LDS atomic ORs that
 //     return no value (two lanes of one instruction may hit one word), flushed at the wavefront's end -- only its non-zero words, with
 //     global atomic ORs, the window's last word masked to set_bits;
@@ -21,12 +20,11 @@
 //     set_words, no value returned; an index outside the window issues nothing (a branch, not a clamp).  SETB_MEM_TEST first loads the
 //     word (cached, through a descriptor bounded to the bitmap) and issues the atomic only when the bit is still clear -- sound because
 //     bits only ever turn on: a stale 0 costs one redundant atomic, a 1 is never stale.
-// inserted / outside are counted per lane from the mask slices and the in-window tests, folded over the wavefront once at its end and
-// added with at most two 64-bit vector atomics (none when stats == nullptr).  A block that fails the mixed-width device checks raises
+// inserted / outside are counted per lane from the mask slices and the in-window tests (folded with wave_sum_u64, fl_block_run.hpp).  A block that fails the mixed-width device checks raises
 // its FL_DEVERR_* bit and contributes nothing.  LDS is wave-local (in-order per wave): no s_barrier.  Every global store or atomic is
 // a vector instruction.
 #pragma once
-#include "fl_aggregate_by.hpp"
+#include "fl_aggregate.hpp"
 #include "fl_set_build_map.hpp"
 
 namespace fl {
@@ -65,14 +63,9 @@ template <typename T> struct SetBuildLoads {
 };
 template <typename T> __device__ __forceinline__ SetBuildLoads<T> set_build_issue(const SetBuildArgs& a, uint64_t blk, unsigned lane)
 {
-    using M = SelectMap<sizeof(T)>;
     SetBuildLoads<T> p;
     p.m = issue_block_loads<T>(a.col, a.refs, blk);
-    static_for<(int)M::GROUPS>([&](auto K) {
-        constexpr unsigned k = decltype(K)::value;
-        p.slice[k] = (1u << M::N) - 1u;                                     // no mask: every row
-        if (a.mask) p.slice[k] = M::slice(a.mask[blk * SELECT_MASK_WORDS + M::mask_word(k, lane)], k, lane);
-    });
+    block_mask_slices<T>(a.mask, blk, lane, p.slice);
     return p;
 }
 
@@ -153,13 +146,6 @@ __device__ __forceinline__ void set_build_block(const SetBuildArgs& a, uint64_t 
     wave_lds_fence();                                                       // the image is reused by the wavefront's next block
 }
 
-__device__ __forceinline__ uint64_t set_build_wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // Workgroup (= wavefront) g owns blocks [g * run, (g + 1) * run) of the column; one that owns none returns at once and flushes nothing.
 template <typename T, int TIER>
 __global__ __launch_bounds__(64) void k_unfor_set_build(SetBuildArgs a)
@@ -194,8 +180,8 @@ __global__ __launch_bounds__(64) void k_unfor_set_build(SetBuildArgs a)
         }
     }
     if (a.stats) {
-        ins = set_build_wave_sum(ins);
-        out = set_build_wave_sum(out);
+        ins = wave_sum_u64(ins);
+        out = wave_sum_u64(out);
         if (lane == 0u && ins != 0ull) __hip_atomic_fetch_add(a.stats, ins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane == 0u && out != 0ull) __hip_atomic_fetch_add(a.stats + 1, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
