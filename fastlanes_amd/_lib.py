@@ -121,38 +121,37 @@ _SIGNATURES = (
     ("AGGREGATE_REDUCE", "fl_aggregate_reduce", _I, [_P, _Z, _P, _P]),
     # FL_DECLARE_AGGREGATE_BY (device tier): count / sum / min / max per u8 key of the rows a mask keeps, 256 slots
     # ({vty}: the element type of the VALUE column -- the key column is always u8.  The recorded refusal matrix of
-    # tests/test_cabi_refusals_cpu.py covers the "{ty}" rows; these rows' refusals are pinned by tests/test_aggregate_by_cpu.py.)
+    # tests/test_cabi_refusals_cpu.py covers the "{ty}" rows in its PER_TYPE and every "{vty}" row below in its PER_VALUE_TYPE.)
     ("AGGREGATE_BY", "fl_{vty}_unfor_aggregate_by", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_BY", "fl_{vty}_unfor_aggregate_by_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
     # FL_DECLARE_FOR_COMPARE_COLUMNS (device tier): a <op> b between two FoR-packed columns of one element type, chained through a mask
-    # ({vty} as above: these rows' refusals are pinned by tests/test_for_compare_columns_cpu.py)
+    # ({vty} as above)
     ("FOR_COMPARE_COLUMNS", "fl_{vty}_unfor_compare_columns", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _P]),
     ("FOR_COMPARE_COLUMNS", "fl_{vty}_unfor_compare_columns_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _I, _I, _I, _P, _Z, _P, _P, _P]),
     # FL_DECLARE_AGGREGATE_COLUMNS (device tier): count / sum / min / max per block of a * b, a + b or a - b between two FoR-packed columns
-    # of one element type under a mask ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_columns_cpu.py)
+    # of one element type under a mask ({vty} as above)
     ("AGGREGATE_COLUMNS", "fl_{vty}_unfor_aggregate_columns", _I, [_I, _U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_COLUMNS", "fl_{vty}_unfor_aggregate_columns_widths", _I, [_I, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
     # FL_DECLARE_FOR_COMPARE_IN (device tier): set membership (a window of the value domain plus a bitmap) chained through a mask
-    # ({vty} as above: these rows' refusals are pinned by tests/test_for_compare_in_cpu.py)
+    # ({vty} as above)
     ("FOR_COMPARE_IN", "fl_{vty}_unfor_compare_in", _I, [_U, _P, _P, _Z, _T, _Q, _P, _I, _I, _P, _Z, _P, _P]),
     ("FOR_COMPARE_IN", "fl_{vty}_unfor_compare_in_widths", _I, [_P, _P, _P, _Z, _P, _Z, _T, _Q, _P, _I, _I, _P, _Z, _P, _P, _P]),
     # FL_DECLARE_AGGREGATE_BY_COLUMNS (device tier): count / sum / min / max per u8 key of a * b, a + b or a - b between two FoR-packed
-    # columns of one element type under a mask ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_by_columns_cpu.py)
+    # columns of one element type under a mask ({vty} as above)
     ("AGGREGATE_BY_COLUMNS", "fl_{vty}_unfor_aggregate_by_columns", _I, [_I, _U, _P, _P, _Z, _U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _P, _P, _P]),
     ("AGGREGATE_BY_COLUMNS", "fl_{vty}_unfor_aggregate_by_columns_widths", _I,
      [_I, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P]),
     # FL_DECLARE_SET_BUILD (device tier): the member set of the values a mask keeps, ORed into a window's bitmap -- the build side of
-    # unfor_compare_in ({vty} as above: these rows' refusals are pinned by tests/test_set_build_cpu.py)
+    # unfor_compare_in ({vty} as above)
     ("SET_BUILD", "fl_{vty}_unfor_set_build", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P]),
     ("SET_BUILD", "fl_{vty}_unfor_set_build_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P]),
     # FL_DECLARE_AGGREGATE_BY_WINDOW (device tier): COUNT / SUM / MIN / MAX per key of a dense window, value and key column of one type,
-    # accumulated into the caller's four arrays ({vty} as above: these rows' refusals are pinned by tests/test_aggregate_by_window_cpu.py)
+    # accumulated into the caller's four arrays ({vty} as above)
     ("AGGREGATE_BY_WINDOW", "fl_{vty}_unfor_aggregate_by_window", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
     ("AGGREGATE_BY_WINDOW", "fl_{vty}_unfor_aggregate_by_window_widths", _I,
      [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P, _P]),
     # FL_DECLARE_LOOKUP (device tier): table[(key - key_lo) mod 2^T] of the rows a mask keeps, the payload of the key's own type, written
-    # in full-width packed order -- the probe side of a payload join ({vty} as above: these rows' refusals are pinned by
-    # tests/test_lookup_cpu.py)
+    # in full-width packed order -- the probe side of a payload join ({vty} as above)
     ("LOOKUP", "fl_{vty}_unfor_lookup", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _T, _P, _P, _P, _P]),
     ("LOOKUP", "fl_{vty}_unfor_lookup_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _T, _P, _P, _P, _P, _P]),
     # FL_DECLARE_LOOKUP_U8 (device tier): the same with a uint8_t payload (for u8 keys the pair above under a second name: every
@@ -160,13 +159,12 @@ _SIGNATURES = (
     ("LOOKUP_U8", "fl_{vty}_unfor_lookup_u8", _I, [_U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _U8, _P, _P, _P, _P]),
     ("LOOKUP_U8", "fl_{vty}_unfor_lookup_u8_widths", _I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _U8, _P, _P, _P, _P, _P]),
     # FL_DECLARE_AGGREGATE_BY_LOOKUP (device tier): unfor_lookup_u8 and unfor_aggregate_by in one pass -- COUNT / SUM / MIN / MAX per u8
-    # attribute fetched through a key column of the value column's own type, no per-row output ({vty} as above: these rows' refusals
-    # are pinned by tests/test_aggregate_by_lookup_cpu.py)
+    # attribute fetched through a key column of the value column's own type, no per-row output ({vty} as above)
     ("AGGREGATE_BY_LOOKUP", "fl_{vty}_unfor_aggregate_by_lookup", _I, [_U, _P, _P, _Z, _U, _P, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
     ("AGGREGATE_BY_LOOKUP", "fl_{vty}_unfor_aggregate_by_lookup_widths", _I,
      [_P, _P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _P, _Z, _P, _Z, _T, _Q, _P, _P, _P, _P, _P, _P]),
     # FL_DECLARE_DELTA_COMPARE_RANGE (device tier): interval predicates over DELTA-packed columns, chained through a mask ({vty} as
-    # above: these rows' refusals are pinned by tests/test_delta_compare_range_cpu.py)
+    # above)
     ("DELTA_COMPARE_RANGE", "fl_{vty}_undelta_compare_range", _I, [_U, _P, _P, _T, _T, _I, _P, _Z, _P, _P]),
     ("DELTA_COMPARE_RANGE", "fl_{vty}_undelta_compare_range_widths", _I, [_P, _P, _P, _Z, _P, _T, _T, _I, _P, _Z, _P, _P, _P]),
 )

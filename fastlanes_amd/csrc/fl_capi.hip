@@ -3,8 +3,11 @@
 // (the reference's `match width`, bitpacking.rs:82-95) and launches it.  No CPU
 // compute path exists in this library: every entry point ends in a HIP launch.
 // In this order: the kernel policy; the builders of the launch-argument blocks and the device tier's validators (run_* / dev_*);
-// fl_mixed_plan; extern "C" -- the public entry points, then the fl_internal_* ones of the A/B tools.  The host tier (HostCtx, host_run)
-// is fl_host_tier.hpp, part of this translation unit; fl_column_pair_alloc / _free and the memory-class probe live in fl_pair.hip.
+// the consumers of a packed column (fl_consumer_tier.hpp, included where what it builds on is defined); fl_mixed_plan; extern "C" --
+// the public entry points, then the fl_internal_* ones of the A/B tools.  Three headers are part of this translation unit alone: the
+// host tier (HostCtx, host_run: fl_host_tier.hpp), the scans (fl_scan.hpp) and the consumer tier (fl_consumer_tier.hpp: the host side
+// of every consumer of a packed column and its entry points).  fl_column_pair_alloc / _free and the memory-class probe live in
+// fl_pair.hip.
 #include "../../include/fastlanes_amd.h"
 #include "../../include/fastlanes_amd_internal.h"
 #include "fl_host.hpp"
@@ -16,20 +19,6 @@
 #include "fl_batch.hpp"
 #include "fl_scan.hpp"
 #include "fl_consume.hpp"
-#include "fl_for_compare.hpp"
-#include "fl_for_compare_range.hpp"
-#include "fl_for_compare_in.hpp"
-#include "fl_aggregate_by_columns.hpp"
-#include "fl_set_build.hpp"
-#include "fl_lookup.hpp"
-#include "fl_aggregate_by_lookup.hpp"
-#include "fl_delta_compare_range.hpp"
-#include "fl_aggregate_by_window.hpp"
-#include "fl_select.hpp"
-#include "fl_aggregate.hpp"
-#include "fl_aggregate_by.hpp"
-#include "fl_for_compare_columns.hpp"
-#include "fl_aggregate_columns.hpp"
 #include "fl_host_tier.hpp"
 
 #include <algorithm>
@@ -114,8 +103,8 @@ struct Column {
     const uint64_t* offsets = nullptr;
     size_t packed_bytes = 0;
 };
-// THE place that fills a WidthsArgs.  refs: FoR's references, null for plain BitPacking -- and for the four consumers, whose kernels
-// load the references with the block's metadata.  The callers differ in the wave shape, which they state.
+// THE place that fills a WidthsArgs.  refs: FoR's references, null for plain BitPacking -- and for the consumers (fl_consumer_tier.hpp:
+// column_args), whose kernels load the references with the block's metadata.  The callers differ in the wave shape, which they state.
 template <typename T>
 void widths_args(WidthsArgs& a, const Column& col, const void* packed, void* unpacked, const void* refs, size_t ref_stride,
                  uint32_t* err_flag, size_t n_blocks, const WaveShape& sh)
@@ -394,544 +383,6 @@ int run_chain_widths(int op, const uint8_t* widths, const uint64_t* offsets, con
     return rc >= 0 ? rc : hip_fail(hipErrorInvalidDeviceFunction);
 }
 
-// The consumers of a FoR-packed column (fl_for_block.hpp): unfor_compare, unfor_compare_range, unfor_select, unfor_aggregate (and
-// unfor_aggregate_by, which takes two of them), each over
-// a uniform-width column (col.width, blocks back to back) or a mixed-width one (widths[] / offsets[], checked per block by the kernel).
-// false: one of the column's pointers is missing (FL_ERR_NULL).  A mixed-width column whose blocks all have width 0 has no packed bytes:
-// its packed pointer may be NULL (run_widths) and is replaced here.
-template <typename T> bool block_consumer_column(const Column& col, const T*& packed, const T* refs)
-{
-    if (col.mixed && !packed && col.packed_bytes == 0) packed = no_bytes<T>();
-    return refs && (!col.mixed || (col.widths && col.offsets)) && (packed || (!col.mixed && col.width == 0));
-}
-// the WidthsArgs part of the four argument blocks, launched with the shape of unfor_pack_widths: the same blocks, the same reads
-template <typename T>
-WaveShape block_consumer_args(WidthsArgs& a, const Column& col, const T* packed, size_t ref_stride, size_t n_blocks, uint32_t* err_flag)
-{
-    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), mixed_blocks_per_wave(Elem<T>::BITS, false), mixed_prefetch(Elem<T>::BITS)});
-    widths_args<T>(a, col, packed, nullptr, nullptr, ref_stride, err_flag, n_blocks, sh);
-    return sh;
-}
-
-// unfor_compare (fl_for_compare.hpp).  The predicate becomes its cyclic interval here, once per call.
-template <typename T>
-int run_unfor_compare(const Column& col, const T* packed, const T* refs, size_t ref_stride, int op, T constant, size_t n_blocks,
-                      uint32_t* mask, uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (op < FL_CMP_EQ || op > FL_CMP_GE) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (!block_consumer_column(col, packed, refs) || !mask) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask)) return FL_ERR_ALIGN;
-    const ForPredicate p = for_compare_predicate(Elem<T>::BITS, op, constant);
-    ForCompareArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
-    a.mask = reinterpret_cast<char*>(mask);
-    a.cmp_refs = refs;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = p.none ? 1u : 0u;
-    return hip_status(for_compare_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_compare_range: run_unfor_compare with the cyclic interval [lo, hi] as the predicate and the mask so far beside it
-// (fl_for_compare_range.hpp).  The same launch shape, the same checks in the same order; `mask` may be `mask_in`.
-template <typename T>
-int run_unfor_compare_range(const Column& col, const T* packed, const T* refs, size_t ref_stride, T lo, T hi, int combine,
-                            const uint32_t* mask_in, size_t n_blocks, uint32_t* mask, uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
-    else if (!mask_in) return FL_ERR_NULL;
-    if (!block_consumer_column(col, packed, refs) || !mask) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
-    const ForPredicate p = for_range_predicate(Elem<T>::BITS, lo, hi);
-    ForRangeArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
-    a.mask = reinterpret_cast<char*>(mask);
-    a.cmp_refs = refs;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = 0u;
-    a.mask_in = reinterpret_cast<const char*>(mask_in);
-    a.combine = (unsigned)combine;
-    return hip_status(for_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// undelta_compare_range (fl_delta_compare_range.hpp): run_unfor_compare_range over a Delta-packed column -- `bases` (LANES per block, 128
-// bytes, read as 16-byte cells) stands where the references stood.  The same checks in the same order, `bases` among the required and
-// the aligned pointers; one block per wavefront for every type, at unfor_pack_widths' occupancy; `mask` may be `mask_in`.
-template <typename T>
-int run_undelta_compare_range(const Column& col, const T* packed, const T* bases, T lo, T hi, int combine, const uint32_t* mask_in,
-                              size_t n_blocks, uint32_t* mask, uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
-    else if (!mask_in) return FL_ERR_NULL;
-    if (!block_consumer_column(col, packed, bases) || !mask) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(bases) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
-    const ForPredicate p = for_range_predicate(Elem<T>::BITS, lo, hi);
-    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), 1u, 0u});
-    DeltaRangeArgs a;
-    widths_args<T>(a, col, packed, nullptr, nullptr, 0, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    a.mask = reinterpret_cast<char*>(mask);
-    a.cmp_refs = nullptr;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = 0u;
-    a.mask_in = reinterpret_cast<const char*>(mask_in);
-    a.combine = (unsigned)combine;
-    a.bases = reinterpret_cast<const char*>(bases);
-    return hip_status(delta_range_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_compare_in: run_unfor_compare_range with the member set's window as the predicate and its bitmap beside it
-// (fl_for_compare_in.hpp, fl_set_decide.hpp).  The same launch shape, the same checks in the same order, the set's own among them:
-// negate and set_bits with combine (FL_ERR_INDEX), set_words with the other pointers (FL_ERR_NULL, FL_ERR_ALIGN; never read when
-// set_bits == 0).  set_bits decides the tier here, once per call: up to SET_REGISTER_BITS the bitmap rides in a VGPR.
-template <typename T>
-int run_unfor_compare_in(const Column& col, const T* packed, const T* refs, size_t ref_stride, T set_lo, uint64_t set_bits,
-                         const uint32_t* set_words, int negate, int combine, const uint32_t* mask_in, size_t n_blocks, uint32_t* mask,
-                         uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (combine < FL_MASK_NEW || combine > FL_MASK_OR || negate < 0 || negate > 1 || set_bits > set_max_bits(Elem<T>::BITS)) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
-    else if (!mask_in) return FL_ERR_NULL;
-    if (set_bits == 0) set_words = nullptr;                              // the empty set: never read, never checked
-    else if (!set_words) return FL_ERR_NULL;
-    if (!block_consumer_column(col, packed, refs) || !mask) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask) || misaligned(mask_in) || misaligned(set_words)) return FL_ERR_ALIGN;
-    const ForPredicate p = set_window(Elem<T>::BITS, set_lo, set_bits);
-    ForInArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
-    a.mask = reinterpret_cast<char*>(mask);
-    a.cmp_refs = refs;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = p.none ? 1u : 0u;
-    a.mask_in = reinterpret_cast<const char*>(mask_in);
-    a.combine = (unsigned)combine;
-    a.set_words = set_words;
-    a.set_bytes = (unsigned)(4u * set_word_count(set_bits));
-    a.negate = (unsigned)negate;
-    return hip_status(for_in_launcher<T>(set_bits <= SET_REGISTER_BITS)(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_set_build (fl_set_build.hpp): the member set unfor_compare_in probes, built from a column under a mask.  The window's checks are
-// run_unfor_compare_in's, in its order: the width; set_bits (FL_ERR_INDEX); the empty column; set_words (never touched when set_bits
-// == 0) and the column's pointers (FL_ERR_NULL); alignment, set_words and stats included.  `mask` and `stats` may be NULL.  set_bits
-// decides the tier here, once per call (fl_set_build_map.hpp: set_build_lds_tier).  The memory tier ships SET_BUILD_MEMORY_TIER; the
-// timing tool measures the other variant beside it through the environment variable FL_INTERNAL_SET_BUILD_VARIANT (1: one atomic per
-// element, 2: test before set; read on every memory-tier call, bits identical either way).  The persistent grid takes the policy's
-// waves and blocks per wavefront as run_unfor_aggregate_by does.
-constexpr int SET_BUILD_MEMORY_TIER = SETB_MEM_TEST;
-inline int set_build_tier(uint64_t set_bits)
-{
-    if (set_build_lds_tier(set_bits)) return SETB_LDS;
-    if (const char* v = std::getenv("FL_INTERNAL_SET_BUILD_VARIANT")) {
-        if (v[0] == '1' && !v[1]) return SETB_MEM;
-        if (v[0] == '2' && !v[1]) return SETB_MEM_TEST;
-    }
-    return SET_BUILD_MEMORY_TIER;
-}
-template <typename T>
-int run_unfor_set_build(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, T set_lo,
-                        uint64_t set_bits, uint32_t* set_words, uint64_t* stats, uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (set_bits > set_max_bits(Elem<T>::BITS)) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (set_bits == 0) set_words = nullptr;                              // the empty window: never touched, never checked
-    else if (!set_words) return FL_ERR_NULL;
-    if (!block_consumer_column(col, packed, refs)) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask) || misaligned(set_words) || misaligned(stats)) return FL_ERR_ALIGN;
-    const ForPredicate p = set_window(Elem<T>::BITS, set_lo, set_bits);
-    const WaveShape sh = with_policy({0, 0u, 0u});
-    SetBuildArgs a;
-    widths_args<T>(a.col, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    a.refs = refs;
-    a.mask = mask;
-    a.set_words = set_words;
-    a.stats = stats;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = p.none ? 1u : 0u;
-    a.n_words = (unsigned)set_word_count(set_bits);
-    a.last_mask = set_build_last_word_mask(set_bits);
-    a.run = 0;
-    const set_build_launch_t fn = set_build_launcher<T>(set_build_tier(set_bits));
-    if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
-    return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_aggregate_by_window (fl_aggregate_by_window.hpp): a value column and a key column of T of the same form, both uniform or both
-// mixed, grouped inside the window [key_lo, key_lo + n_groups - 1] into the caller's four arrays.  One validator, one builder.
-// The validator's order is run_unfor_set_build's: the widths; n_groups (FL_ERR_INDEX); the empty column; the columns' pointers
-// (FL_ERR_NULL; the four arrays, `mask` and `stats` may be NULL); alignment, the arrays and stats included.  An empty window touches no
-// array: the builder drops them, so they are neither maintained nor checked.
-struct WindowArrays {
-    uint64_t *counts, *sums, *mins, *maxs, *stats;
-};
-template <typename T>
-int aggregate_by_window_refusal(const Column& col, const T*& packed, const T* refs, const Column& kcol, const T*& keys, const T* key_refs,
-                                const uint32_t* mask, size_t n_blocks, uint64_t n_groups, WindowArrays& t)
-{
-    if ((!col.mixed && over_width<T>(col.width)) || (!kcol.mixed && over_width<T>(kcol.width))) return FL_ERR_WIDTH;
-    if (n_groups > aggregate_by_window_max_groups(Elem<T>::BITS)) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (n_groups == 0) t.counts = t.sums = t.mins = t.maxs = nullptr;    // the empty window: never touched, never checked
-    if (!block_consumer_column(col, packed, refs) || !block_consumer_column(kcol, keys, key_refs)) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(keys) || misaligned(mask) || misaligned(t.counts) || misaligned(t.sums) || misaligned(t.mins) ||
-        misaligned(t.maxs) || misaligned(t.stats))
-        return FL_ERR_ALIGN;
-    return FL_OK;
-}
-template <typename T>
-AggregateByWindowArgs aggregate_by_window_args(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
-                                               const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
-                                               uint64_t n_groups, const WindowArrays& t, uint32_t* err_flag, const WaveShape& sh)
-{
-    const ForPredicate p = set_window(Elem<T>::BITS, key_lo, n_groups);
-    AggregateByWindowArgs a;
-    widths_args<T>(a.val, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    widths_args<T>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    a.val_refs = refs;
-    a.key_refs = key_refs;
-    a.mask = mask;
-    a.counts = t.counts;
-    a.sums = t.sums;
-    a.mins = t.mins;
-    a.maxs = t.maxs;
-    a.stats = t.stats;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = p.none ? 1u : 0u;
-    a.need_values = t.sums || t.mins || t.maxs ? 1u : 0u;
-    a.n_slots = aggregate_by_window_lds_tier(n_groups) ? (unsigned)n_groups : 0u;
-    a.run = 0;
-    return a;
-}
-template <typename T>
-int run_unfor_aggregate_by_window(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
-                                  const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo, uint64_t n_groups,
-                                  WindowArrays t, uint32_t* err_flag, void* stream)
-{
-    if (const int rc = aggregate_by_window_refusal<T>(col, packed, refs, kcol, keys, key_refs, mask, n_blocks, n_groups, t); rc != FL_OK || n_blocks == 0)
-        return rc;
-    const WaveShape sh = with_policy({0, 0u, 0u});
-    const AggregateByWindowArgs a =
-        aggregate_by_window_args<T>(col, packed, refs, ref_stride, kcol, keys, key_refs, key_ref_stride, mask, n_blocks, key_lo, n_groups, t, err_flag, sh);
-    const aggregate_by_window_launch_t fn = aggregate_by_window_launcher<T>(aggregate_by_window_lds_tier(n_groups) ? AGGW_LDS : AGGW_MEM);
-    if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
-    return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_lookup (fl_lookup.hpp): table[(key - key_lo) mod 2^T] of every kept row of a key column, U = T or uint8_t, written in full-width
-// packed order with the hits as a mask beside it.  One validator, one builder.  The validator's order is run_unfor_set_build's: the
-// width; n_slots (FL_ERR_INDEX: above min(2^T, 2^32) slots, or a table of 2^31 bytes or more); the empty column; `table` (never read
-// when n_slots == 0), `out` and the column's pointers (FL_ERR_NULL; `mask`, `present`, `hit_mask` and `stats` may be NULL); alignment.
-// An empty window reads neither the table nor the bitmap: the validator drops them, so they are neither read nor checked.  n_slots
-// decides the tier here, once per call (fl_lookup_map.hpp: lookup_tier).  The persistent grid takes the policy's waves and blocks per
-// wavefront as run_unfor_set_build does.
-struct LookupTable {
-    const void* table;
-    const uint32_t* present;
-    uint64_t missing;
-    void* out;
-    uint32_t* hit_mask;
-    uint64_t* stats;
-};
-template <typename T>
-int lookup_refusal(const Column& col, const T*& packed, const T* refs, const uint32_t* mask, size_t n_blocks, uint64_t n_slots, unsigned payload_bytes,
-                   LookupTable& t)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (lookup_slots_refused(Elem<T>::BITS, n_slots, payload_bytes)) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (n_slots == 0) t.table = t.present = nullptr;                      // the empty window: never read, never checked
-    else if (!t.table) return FL_ERR_NULL;
-    if (!block_consumer_column(col, packed, refs) || !t.out) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask) || misaligned(t.hit_mask) || misaligned(t.present) || misaligned(t.table) || misaligned(t.out) ||
-        misaligned(t.stats))
-        return FL_ERR_ALIGN;
-    return FL_OK;
-}
-template <typename T>
-LookupArgs lookup_args(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
-                       uint64_t n_slots, unsigned payload_bytes, const LookupTable& t, uint32_t* err_flag, const WaveShape& sh)
-{
-    const ForPredicate p = set_window(Elem<T>::BITS, key_lo, n_slots);
-    LookupArgs a;
-    widths_args<T>(a.col, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    a.refs = refs;
-    a.mask = mask;
-    a.table = t.table;
-    a.present = t.present;
-    a.out = static_cast<char*>(t.out);
-    a.hit_mask = t.hit_mask;
-    a.stats = t.stats;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.missing = t.missing;
-    a.cmp_none = p.none ? 1u : 0u;
-    a.table_bytes = (unsigned)(n_slots * payload_bytes);
-    a.present_bytes = t.present ? (unsigned)(4u * set_word_count(n_slots)) : 0u;
-    a.run = 0;
-    return a;
-}
-template <typename T>
-int run_unfor_lookup(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
-                     uint64_t n_slots, unsigned payload_bytes, LookupTable t, uint32_t* err_flag, void* stream)
-{
-    if (const int rc = lookup_refusal<T>(col, packed, refs, mask, n_blocks, n_slots, payload_bytes, t); rc != FL_OK || n_blocks == 0) return rc;
-    const WaveShape sh = with_policy({0, 0u, 0u});
-    const LookupArgs a = lookup_args<T>(col, packed, refs, ref_stride, mask, n_blocks, key_lo, n_slots, payload_bytes, t, err_flag, sh);
-    const lookup_launch_t fn = lookup_launcher<T>(payload_bytes, lookup_tier(n_slots, payload_bytes));
-    if (!fn) return hip_fail(hipErrorInvalidDeviceFunction);
-    return hip_status(fn(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_aggregate_by_lookup (fl_aggregate_by_lookup.hpp): unfor_lookup_u8 and unfor_aggregate_by in one pass -- a value column and a key
-// column of T of the same form, both uniform or both mixed, a u8 table over the window [key_lo, key_lo + n_slots - 1], 256 groups.  One
-// validator, one builder.  The validator's order is that of the two parents: the widths; n_slots (FL_ERR_INDEX, lookup_slots_refused with
-// a one-byte payload); `result` (written by EVERY call -- the init launch also answers an empty column -- so it is required before the
-// empty-column return), `table` (never read when n_slots == 0: the validator drops it and `present`, so they are neither read nor
-// checked) and the columns' pointers (FL_ERR_NULL; `mask`, `present` and `stats` may be NULL); alignment.  The persistent grid takes
-// the policy's waves and blocks per wavefront as run_unfor_aggregate_by does.
-struct LookupGroups {
-    const uint8_t* table;
-    const uint32_t* present;
-    void* result;
-    uint64_t* stats;
-};
-template <typename T>
-int aggregate_by_lookup_refusal(const Column& col, const T*& packed, const T* refs, const Column& kcol, const T*& keys, const T* key_refs,
-                                const uint32_t* mask, size_t n_blocks, uint64_t n_slots, LookupGroups& t)
-{
-    if ((!col.mixed && over_width<T>(col.width)) || (!kcol.mixed && over_width<T>(kcol.width))) return FL_ERR_WIDTH;
-    if (lookup_slots_refused(Elem<T>::BITS, n_slots, 1u)) return FL_ERR_INDEX;
-    if (!t.result) return FL_ERR_NULL;
-    if (n_blocks) {
-        if (n_slots == 0) {                                              // the empty window: never read, never checked
-            t.table = nullptr;
-            t.present = nullptr;
-        } else if (!t.table) {
-            return FL_ERR_NULL;
-        }
-        if (!block_consumer_column(col, packed, refs) || !block_consumer_column(kcol, keys, key_refs)) return FL_ERR_NULL;
-        if (misaligned(packed) || misaligned(keys) || misaligned(mask) || misaligned(t.present) || misaligned(t.table) || misaligned(t.stats))
-            return FL_ERR_ALIGN;
-    }
-    return misaligned(t.result) ? FL_ERR_ALIGN : FL_OK;
-}
-template <typename T>
-AggregateByLookupArgs aggregate_by_lookup_args(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
-                                               const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo,
-                                               uint64_t n_slots, const LookupGroups& t, uint32_t* err_flag, const WaveShape& sh)
-{
-    const ForPredicate p = set_window(Elem<T>::BITS, key_lo, n_slots);
-    AggregateByLookupArgs a;
-    widths_args<T>(a.val, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    widths_args<T>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    a.val_refs = refs;
-    a.key_refs = key_refs;
-    a.mask = mask;
-    a.table = t.table;
-    a.present = t.present;
-    a.result = static_cast<BlockAggregate*>(t.result);
-    a.stats = t.stats;
-    a.cmp_a = p.a;
-    a.cmp_s = p.s;
-    a.cmp_none = p.none ? 1u : 0u;
-    a.table_bytes = (unsigned)n_slots;
-    a.present_bytes = t.present ? (unsigned)(4u * set_word_count(n_slots)) : 0u;
-    a.run = 0;
-    return a;
-}
-template <typename T>
-int run_unfor_aggregate_by_lookup(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const T* keys,
-                                  const T* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, T key_lo, uint64_t n_slots,
-                                  LookupGroups t, uint32_t* err_flag, void* stream)
-{
-    if (const int rc = aggregate_by_lookup_refusal<T>(col, packed, refs, kcol, keys, key_refs, mask, n_blocks, n_slots, t); rc != FL_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipError_t e = launch_aggregate_by_init(static_cast<BlockAggregate*>(t.result), s); e != hipSuccess || n_blocks == 0) return hip_status(e);
-    const WaveShape sh = with_policy({0, 0u, 0u});
-    const AggregateByLookupArgs a =
-        aggregate_by_lookup_args<T>(col, packed, refs, ref_stride, kcol, keys, key_refs, key_ref_stride, mask, n_blocks, key_lo, n_slots, t, err_flag, sh);
-    return hip_status(aggregate_by_lookup_launcher<T>()(a, sh.waves, s));
-}
-
-// unfor_compare_columns (fl_for_compare_columns.hpp): two columns of T of the same form, both uniform or both mixed.  The six ops become
-// one base relation, "swap the columns" and "invert" here, once per call (fl_columns_decide.hpp: columns_relation); the swap is done
-// here, so the kernel's column a is always the base relation's left side.  The launch shape and the order of the checks are those of
-// run_unfor_compare_range; `mask` may be `mask_in`.
-template <typename T>
-int run_unfor_compare_columns(const Column& cola, const T* a_packed, const T* a_refs, size_t a_ref_stride, const Column& colb, const T* b_packed,
-                              const T* b_refs, size_t b_ref_stride, int op, int is_signed, int combine, const uint32_t* mask_in,
-                              size_t n_blocks, uint32_t* mask, uint32_t* err_flag, void* stream)
-{
-    if ((!cola.mixed && over_width<T>(cola.width)) || (!colb.mixed && over_width<T>(colb.width))) return FL_ERR_WIDTH;
-    if (op < FL_CMP_EQ || op > FL_CMP_GE || combine < FL_MASK_NEW || combine > FL_MASK_OR) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (combine == FL_MASK_NEW) mask_in = nullptr;                       // ignored: never read, never checked
-    else if (!mask_in) return FL_ERR_NULL;
-    if (!block_consumer_column(cola, a_packed, a_refs) || !block_consumer_column(colb, b_packed, b_refs) || !mask) return FL_ERR_NULL;
-    if (misaligned(a_packed) || misaligned(b_packed) || misaligned(mask) || misaligned(mask_in)) return FL_ERR_ALIGN;
-    const ColumnsRelation rel = columns_relation(op);
-    ForColumnsArgs a;
-    uint32_t* ef = cola.mixed ? err_flag : nullptr;
-    const WaveShape sh = rel.swap ? block_consumer_args<T>(a, colb, b_packed, b_ref_stride, n_blocks, ef)
-                                  : block_consumer_args<T>(a, cola, a_packed, a_ref_stride, n_blocks, ef);
-    if (rel.swap) block_consumer_args<T>(a.b, cola, a_packed, a_ref_stride, n_blocks, ef);
-    else block_consumer_args<T>(a.b, colb, b_packed, b_ref_stride, n_blocks, ef);
-    a.mask = reinterpret_cast<char*>(mask);
-    a.cmp_refs = rel.swap ? b_refs : a_refs;
-    a.b_refs = rel.swap ? a_refs : b_refs;
-    a.cmp_a = a.cmp_s = 0;
-    a.cmp_none = 0u;
-    a.mask_in = reinterpret_cast<const char*>(mask_in);
-    a.combine = (unsigned)combine;
-    a.bias = columns_bias(Elem<T>::BITS, is_signed != 0);
-    a.is_eq = rel.is_eq ? 1u : 0u;
-    a.invert = rel.invert ? 1u : 0u;
-    return hip_status(for_columns_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_select (fl_select.hpp).  Launched with the shape of unfor_pack_widths, as unfor_compare is.
-template <typename T>
-int run_unfor_select(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, const uint64_t* out_offsets,
-                     T* out, size_t out_len, size_t n_blocks, uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (n_blocks == 0) return FL_OK;
-    // a selection that keeps nothing has no output: `out` may be NULL with out_len == 0 (a non-empty block then fails the kernel's
-    // bounds check; nothing is ever written through this pointer)
-    if (!out && out_len == 0) out = const_cast<T*>(no_bytes<T>());
-    if (!block_consumer_column(col, packed, refs) || !mask || !out_offsets || !out) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask) || misaligned(out)) return FL_ERR_ALIGN;
-    SelectArgs a;
-    // err_flag for a uniform-width column too, the only consumer that takes one: this form raises FL_DEVERR_BOUNDS (a run outside `out`)
-    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, err_flag);
-    a.mask = mask;
-    a.out_offsets = out_offsets;
-    a.out = reinterpret_cast<char*>(out);
-    a.out_len = out_len;
-    a.sel_refs = refs;
-    return hip_status(select_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_aggregate (fl_aggregate.hpp: a block that fails the kernel's checks leaves the identity in its slot).  Launched with the shape of
-// unfor_pack_widths, as unfor_select is.  `mask` may be NULL: every row is kept and no mask is read.
-template <typename T>
-int run_unfor_aggregate(const Column& col, const T* packed, const T* refs, size_t ref_stride, const uint32_t* mask, size_t n_blocks,
-                        void* block_aggs, uint32_t* err_flag, void* stream)
-{
-    if (!col.mixed && over_width<T>(col.width)) return FL_ERR_WIDTH;
-    if (n_blocks == 0) return FL_OK;
-    if (!block_consumer_column(col, packed, refs) || !block_aggs) return FL_ERR_NULL;
-    if (misaligned(packed) || misaligned(mask) || misaligned(block_aggs)) return FL_ERR_ALIGN;
-    AggregateArgs a;
-    const WaveShape sh = block_consumer_args<T>(a, col, packed, ref_stride, n_blocks, col.mixed ? err_flag : nullptr);
-    a.mask = mask;
-    a.aggs = static_cast<char*>(block_aggs);
-    a.agg_refs = refs;
-    return hip_status(aggregate_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_aggregate_columns (fl_aggregate_columns.hpp): two columns of T of the same form, both uniform or both mixed, met element by
-// element under `expr` and aggregated per block as run_unfor_aggregate does (a block that fails either column's checks leaves the
-// identity in its slot).  The same launch shape; the checks in the order of run_unfor_aggregate, `expr` where a `combine` is judged.
-template <typename T>
-int run_unfor_aggregate_columns(int expr, const Column& cola, const T* a_packed, const T* a_refs, size_t a_ref_stride, const Column& colb,
-                                const T* b_packed, const T* b_refs, size_t b_ref_stride, const uint32_t* mask, size_t n_blocks,
-                                void* block_aggs, uint32_t* err_flag, void* stream)
-{
-    if ((!cola.mixed && over_width<T>(cola.width)) || (!colb.mixed && over_width<T>(colb.width))) return FL_ERR_WIDTH;
-    if (!expr_valid(expr)) return FL_ERR_INDEX;
-    if (n_blocks == 0) return FL_OK;
-    if (!block_consumer_column(cola, a_packed, a_refs) || !block_consumer_column(colb, b_packed, b_refs) || !block_aggs) return FL_ERR_NULL;
-    if (misaligned(a_packed) || misaligned(b_packed) || misaligned(mask) || misaligned(block_aggs)) return FL_ERR_ALIGN;
-    AggregateColumnsArgs a;
-    uint32_t* ef = cola.mixed ? err_flag : nullptr;
-    const WaveShape sh = block_consumer_args<T>(a, cola, a_packed, a_ref_stride, n_blocks, ef);
-    block_consumer_args<T>(a.b, colb, b_packed, b_ref_stride, n_blocks, ef);
-    a.mask = mask;
-    a.aggs = static_cast<char*>(block_aggs);
-    a.agg_refs = a_refs;
-    a.b_refs = b_refs;
-    a.expr = (unsigned)expr;
-    return hip_status(aggregate_columns_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
-}
-
-// unfor_aggregate_by (fl_aggregate_by.hpp): a value column of T and a u8 key column of the same form, both uniform or both mixed; a
-// block that fails either column's checks contributes nothing.  `result` (256 slots) is written by EVERY call -- the init launch also
-// answers an empty column -- so it is required and checked before the empty-column return.  The persistent grid takes the policy's
-// waves as its residency and the policy's blocks per wavefront as the least length of a wavefront's run (0: the column divided evenly).
-template <typename T>
-int run_unfor_aggregate_by(const Column& col, const T* packed, const T* refs, size_t ref_stride, const Column& kcol, const uint8_t* keys,
-                           const uint8_t* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, void* result,
-                           uint32_t* err_flag, void* stream)
-{
-    if ((!col.mixed && over_width<T>(col.width)) || (!kcol.mixed && over_width<uint8_t>(kcol.width))) return FL_ERR_WIDTH;
-    if (!result) return FL_ERR_NULL;
-    if (n_blocks && (!block_consumer_column(col, packed, refs) || !block_consumer_column(kcol, keys, key_refs))) return FL_ERR_NULL;
-    if ((n_blocks && (misaligned(packed) || misaligned(keys) || misaligned(mask))) || misaligned(result)) return FL_ERR_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipError_t e = launch_aggregate_by_init(static_cast<BlockAggregate*>(result), s); e != hipSuccess || n_blocks == 0) return hip_status(e);
-    const WaveShape sh = with_policy({0, 0u, 0u});
-    AggregateByArgs a;
-    widths_args<T>(a.val, col, packed, nullptr, nullptr, ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    widths_args<uint8_t>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, col.mixed ? err_flag : nullptr, n_blocks, sh);
-    a.val_refs = refs;
-    a.key_refs = key_refs;
-    a.mask = mask;
-    a.result = static_cast<BlockAggregate*>(result);
-    a.run = 0;
-    return hip_status(aggregate_by_launcher<T>()(a, sh.waves, s));
-}
-
-// unfor_aggregate_by_columns (fl_aggregate_by_columns.hpp): two value columns of T met under `expr` and a u8 key column, all three of
-// the same form, uniform or mixed; a block that fails any column's checks contributes nothing.  The checks of run_unfor_aggregate_by
-// in its order, `expr` where run_unfor_aggregate_columns judges it; `result` and the persistent grid as run_unfor_aggregate_by has them.
-template <typename T>
-int run_unfor_aggregate_by_columns(int expr, const Column& cola, const T* a_packed, const T* a_refs, size_t a_ref_stride, const Column& colb,
-                                   const T* b_packed, const T* b_refs, size_t b_ref_stride, const Column& kcol, const uint8_t* keys,
-                                   const uint8_t* key_refs, size_t key_ref_stride, const uint32_t* mask, size_t n_blocks, void* result,
-                                   uint32_t* err_flag, void* stream)
-{
-    if ((!cola.mixed && over_width<T>(cola.width)) || (!colb.mixed && over_width<T>(colb.width)) || (!kcol.mixed && over_width<uint8_t>(kcol.width)))
-        return FL_ERR_WIDTH;
-    if (!expr_valid(expr)) return FL_ERR_INDEX;
-    if (!result) return FL_ERR_NULL;
-    if (n_blocks && (!block_consumer_column(cola, a_packed, a_refs) || !block_consumer_column(colb, b_packed, b_refs) ||
-                     !block_consumer_column(kcol, keys, key_refs)))
-        return FL_ERR_NULL;
-    if ((n_blocks && (misaligned(a_packed) || misaligned(b_packed) || misaligned(keys) || misaligned(mask))) || misaligned(result)) return FL_ERR_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipError_t e = launch_aggregate_by_init(static_cast<BlockAggregate*>(result), s); e != hipSuccess || n_blocks == 0) return hip_status(e);
-    const WaveShape sh = with_policy({0, 0u, 0u});
-    AggregateByColumnsArgs a;
-    uint32_t* ef = cola.mixed ? err_flag : nullptr;
-    widths_args<T>(a.a, cola, a_packed, nullptr, nullptr, a_ref_stride, ef, n_blocks, sh);
-    widths_args<T>(a.b, colb, b_packed, nullptr, nullptr, b_ref_stride, ef, n_blocks, sh);
-    widths_args<uint8_t>(a.key, kcol, keys, nullptr, nullptr, key_ref_stride, ef, n_blocks, sh);
-    a.a_refs = a_refs;
-    a.b_refs = b_refs;
-    a.key_refs = key_refs;
-    a.mask = mask;
-    a.result = static_cast<BlockAggregate*>(result);
-    a.run = 0;
-    a.expr = (unsigned)expr;
-    return hip_status(aggregate_by_columns_launcher<T>()(a, sh.waves, s));
-}
-
 template <typename T> int dev_for_widths(const T* mins, const T* maxs, size_t n, uint8_t* widths, void* s)
 {
     if (n == 0) return FL_OK;
@@ -990,6 +441,12 @@ int run_batch_chain(int op, const void* const* packed, const void* const* bases,
 }
 
 }  // namespace
+
+// THE list of the element types: M(T, S) once per type and its symbol infix
+#define FL_FOR_EACH_TYPE(M) M(uint8_t, u8) M(uint16_t, u16) M(uint32_t, u32) M(uint64_t, u64)
+
+// the consumers of a packed column (unfor_compare ... undelta_compare_range), host side and extern "C", on what is defined above
+#include "fl_consumer_tier.hpp"
 
 // ---------------------------------------------------------------------------
 // mixed-width columns with the widths kept by the library: device-resident widths[] / offsets[] behind a handle
@@ -1167,11 +624,6 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
     { FL_DEVICE_TIER(s, in, sums); return dev_unpack_block_sums<T>(w, in, n, sums, s); }                                               \
     int fl_##S##_unpack_compare(unsigned w, const T* in, int op, T k, size_t n, uint32_t* mask, void* s)  \
     { FL_DEVICE_TIER(s, in, mask); return dev_unpack_compare<T>(w, in, op, k, n, mask, s); }                                           \
-    int fl_##S##_unfor_compare(unsigned w, const T* in, const T* r, size_t rs, int op, T k, size_t n, uint32_t* mask, void* s) \
-    { FL_DEVICE_TIER(s, in, r, mask); return run_unfor_compare<T>({false, w}, in, r, rs, op, k, n, mask, nullptr, s); } \
-    int fl_##S##_unfor_compare_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, int op, T k, \
-                                      size_t n, uint32_t* mask, uint32_t* ef, void* s)                   \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, ef); return run_unfor_compare<T>({true, 0, w, o, pb}, pk, r, rs, op, k, n, mask, ef, s); }     \
     int fl_##S##_block_min_max(const T* in, size_t n, T* mins, T* maxs, void* s)                          \
     { FL_DEVICE_TIER(s, in, mins, maxs); return dev_block_min_max<T>(in, n, mins, maxs, s); }                                                \
     int fl_##S##_transpose(const T* in, T* out, size_t n, void* s) { FL_DEVICE_TIER(s, in, out); return dev_transpose<T>(false, in, out, n, s); } \
@@ -1273,243 +725,7 @@ size_t fl_packed_len(unsigned type_bits, unsigned width)
                            [&](const T* di, const T*, T* d_o, void* st) { return dev_transpose<T>(true, di, d_o, n, st); }); \
     }
 
-#define FL_DEFINE_SELECT(T, S)                                                                            \
-    int fl_##S##_unfor_select(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, const uint64_t* oo, T* out, size_t ol, \
-                              size_t n, uint32_t* ef, void* s)                                            \
-    { FL_DEVICE_TIER(s, in, r, mask, oo, out, ef); return run_unfor_select<T>({false, w}, in, r, rs, mask, oo, out, ol, n, ef, s); } \
-    int fl_##S##_unfor_select_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
-                                     const uint64_t* oo, T* out, size_t ol, size_t n, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, oo, out, ef); return run_unfor_select<T>({true, 0, w, o, pb}, pk, r, rs, mask, oo, out, ol, n, ef, s); }
-
-FL_DEFINE_SELECT(uint8_t, u8)
-FL_DEFINE_SELECT(uint16_t, u16)
-FL_DEFINE_SELECT(uint32_t, u32)
-FL_DEFINE_SELECT(uint64_t, u64)
-
-#define FL_DEFINE_AGGREGATE(T, S)                                                                         \
-    int fl_##S##_unfor_aggregate(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, \
-                                 void* s)                                                                 \
-    { FL_DEVICE_TIER(s, in, r, mask, aggs, ef); return run_unfor_aggregate<T>({false, w}, in, r, rs, mask, n, aggs, ef, s); } \
-    int fl_##S##_unfor_aggregate_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
-                                        size_t n, void* aggs, uint32_t* ef, void* s)                      \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, aggs, ef); return run_unfor_aggregate<T>({true, 0, w, o, pb}, pk, r, rs, mask, n, aggs, ef, s); }
-
-FL_DEFINE_AGGREGATE(uint8_t, u8)
-FL_DEFINE_AGGREGATE(uint16_t, u16)
-FL_DEFINE_AGGREGATE(uint32_t, u32)
-FL_DEFINE_AGGREGATE(uint64_t, u64)
-
-#define FL_DEFINE_AGGREGATE_BY(T, S)                                                                      \
-    int fl_##S##_unfor_aggregate_by(unsigned w, const T* in, const T* r, size_t rs, unsigned kw, const uint8_t* k, const uint8_t* kr, size_t krs, \
-                                    const uint32_t* mask, size_t n, void* res, uint32_t* ef, void* s)     \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, in, r, k, kr, mask, res, ef);                                                   \
-        return run_unfor_aggregate_by<T>({false, w}, in, r, rs, {false, kw}, k, kr, krs, mask, n, res, ef, s); \
-    }                                                                                                     \
-    int fl_##S##_unfor_aggregate_by_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint8_t* kw, \
-                                           const uint64_t* ko, const uint8_t* k, size_t kb, const uint8_t* kr, size_t krs, const uint32_t* mask, \
-                                           size_t n, void* res, uint32_t* ef, void* s)                    \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, w, o, pk, r, kw, ko, k, kr, mask, res, ef);                                     \
-        return run_unfor_aggregate_by<T>({true, 0, w, o, pb}, pk, r, rs, {true, 0, kw, ko, kb}, k, kr, krs, mask, n, res, ef, s); \
-    }
-
-FL_DEFINE_AGGREGATE_BY(uint8_t, u8)
-FL_DEFINE_AGGREGATE_BY(uint16_t, u16)
-FL_DEFINE_AGGREGATE_BY(uint32_t, u32)
-FL_DEFINE_AGGREGATE_BY(uint64_t, u64)
-
-#define FL_DEFINE_AGGREGATE_BY_COLUMNS(T, S)                                                              \
-    int fl_##S##_unfor_aggregate_by_columns(int ex, unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, \
-                                            size_t brs, unsigned kw, const uint8_t* k, const uint8_t* kr, size_t krs, const uint32_t* mask, \
-                                            size_t n, void* res, uint32_t* ef, void* s)                   \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, a, ar, b, br, k, kr, mask, res, ef);                                            \
-        return run_unfor_aggregate_by_columns<T>(ex, {false, wa}, a, ar, ars, {false, wb}, b, br, brs, {false, kw}, k, kr, krs, mask, n, res, ef, s); \
-    }                                                                                                     \
-    int fl_##S##_unfor_aggregate_by_columns_widths(int ex, const uint8_t* aw, const uint64_t* ao, const T* a, size_t ab, const T* ar, size_t ars, \
-                                                   const uint8_t* bw, const uint64_t* bo, const T* b, size_t bb, const T* br, size_t brs, \
-                                                   const uint8_t* kw, const uint64_t* ko, const uint8_t* k, size_t kb, const uint8_t* kr, \
-                                                   size_t krs, const uint32_t* mask, size_t n, void* res, uint32_t* ef, void* s) \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, aw, ao, a, ar, bw, bo, b, br, kw, ko, k, kr, mask, res, ef);                    \
-        return run_unfor_aggregate_by_columns<T>(ex, {true, 0, aw, ao, ab}, a, ar, ars, {true, 0, bw, bo, bb}, b, br, brs, {true, 0, kw, ko, kb}, k, \
-                                                 kr, krs, mask, n, res, ef, s);                           \
-    }
-
-FL_DEFINE_AGGREGATE_BY_COLUMNS(uint8_t, u8)
-FL_DEFINE_AGGREGATE_BY_COLUMNS(uint16_t, u16)
-FL_DEFINE_AGGREGATE_BY_COLUMNS(uint32_t, u32)
-FL_DEFINE_AGGREGATE_BY_COLUMNS(uint64_t, u64)
-
-#define FL_DEFINE_SET_BUILD(T, S)                                                                         \
-    int fl_##S##_unfor_set_build(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, T lo, uint64_t sb, \
-                                 uint32_t* sw, uint64_t* st, void* s)                                     \
-    { FL_DEVICE_TIER(s, in, r, mask, sw, st); return run_unfor_set_build<T>({false, w}, in, r, rs, mask, n, lo, sb, sw, st, nullptr, s); } \
-    int fl_##S##_unfor_set_build_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
-                                        size_t n, T lo, uint64_t sb, uint32_t* sw, uint64_t* st, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mask, sw, st, ef); return run_unfor_set_build<T>({true, 0, w, o, pb}, pk, r, rs, mask, n, lo, sb, sw, st, ef, s); }
-
-FL_DEFINE_SET_BUILD(uint8_t, u8)
-FL_DEFINE_SET_BUILD(uint16_t, u16)
-FL_DEFINE_SET_BUILD(uint32_t, u32)
-FL_DEFINE_SET_BUILD(uint64_t, u64)
-
-#define FL_DEFINE_AGGREGATE_BY_WINDOW(T, S)                                                               \
-    int fl_##S##_unfor_aggregate_by_window(unsigned w, const T* in, const T* r, size_t rs, unsigned kw, const T* k, const T* kr, size_t krs, \
-                                           const uint32_t* mask, size_t n, T lo, uint64_t ng, uint64_t* cn, uint64_t* sm, uint64_t* mn, \
-                                           uint64_t* mx, uint64_t* st, void* s)                           \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, in, r, k, kr, mask, cn, sm, mn, mx, st);                                        \
-        return run_unfor_aggregate_by_window<T>({false, w}, in, r, rs, {false, kw}, k, kr, krs, mask, n, lo, ng, {cn, sm, mn, mx, st}, nullptr, s); \
-    }                                                                                                     \
-    int fl_##S##_unfor_aggregate_by_window_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, \
-                                                  const uint8_t* kw, const uint64_t* ko, const T* k, size_t kb, const T* kr, size_t krs, \
-                                                  const uint32_t* mask, size_t n, T lo, uint64_t ng, uint64_t* cn, uint64_t* sm, uint64_t* mn, \
-                                                  uint64_t* mx, uint64_t* st, uint32_t* ef, void* s)      \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, w, o, pk, r, kw, ko, k, kr, mask, cn, sm, mn, mx, st, ef);                      \
-        return run_unfor_aggregate_by_window<T>({true, 0, w, o, pb}, pk, r, rs, {true, 0, kw, ko, kb}, k, kr, krs, mask, n, lo, ng, \
-                                                {cn, sm, mn, mx, st}, ef, s);                             \
-    }
-
-FL_DEFINE_AGGREGATE_BY_WINDOW(uint8_t, u8)
-FL_DEFINE_AGGREGATE_BY_WINDOW(uint16_t, u16)
-FL_DEFINE_AGGREGATE_BY_WINDOW(uint32_t, u32)
-FL_DEFINE_AGGREGATE_BY_WINDOW(uint64_t, u64)
-
-#define FL_DEFINE_LOOKUP_FORMS(T, S, U, NAME)                                                              \
-    int fl_##S##_##NAME(unsigned w, const T* in, const T* r, size_t rs, const uint32_t* mask, size_t n, T lo, uint64_t ns, const U* tb, \
-                        const uint32_t* pr, U ms, U* out, uint32_t* hm, uint64_t* st, void* s)            \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, in, r, mask, tb, pr, out, hm, st);                                              \
-        return run_unfor_lookup<T>({false, w}, in, r, rs, mask, n, lo, ns, (unsigned)sizeof(U), {tb, pr, ms, out, hm, st}, nullptr, s); \
-    }                                                                                                     \
-    int fl_##S##_##NAME##_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, const uint32_t* mask, \
-                                 size_t n, T lo, uint64_t ns, const U* tb, const uint32_t* pr, U ms, U* out, uint32_t* hm, uint64_t* st, \
-                                 uint32_t* ef, void* s)                                                   \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, w, o, pk, r, mask, tb, pr, out, hm, st, ef);                                    \
-        return run_unfor_lookup<T>({true, 0, w, o, pb}, pk, r, rs, mask, n, lo, ns, (unsigned)sizeof(U), {tb, pr, ms, out, hm, st}, ef, s); \
-    }
-#define FL_DEFINE_LOOKUP(T, S) FL_DEFINE_LOOKUP_FORMS(T, S, T, unfor_lookup)
-#define FL_DEFINE_LOOKUP_U8(T, S) FL_DEFINE_LOOKUP_FORMS(T, S, uint8_t, unfor_lookup_u8)
-
-FL_DEFINE_LOOKUP(uint8_t, u8)
-FL_DEFINE_LOOKUP(uint16_t, u16)
-FL_DEFINE_LOOKUP(uint32_t, u32)
-FL_DEFINE_LOOKUP(uint64_t, u64)
-FL_DEFINE_LOOKUP_U8(uint8_t, u8)
-FL_DEFINE_LOOKUP_U8(uint16_t, u16)
-FL_DEFINE_LOOKUP_U8(uint32_t, u32)
-FL_DEFINE_LOOKUP_U8(uint64_t, u64)
-
-#define FL_DEFINE_AGGREGATE_BY_LOOKUP(T, S)                                                               \
-    int fl_##S##_unfor_aggregate_by_lookup(unsigned w, const T* in, const T* r, size_t rs, unsigned kw, const T* k, const T* kr, size_t krs, \
-                                           const uint32_t* mask, size_t n, T lo, uint64_t ns, const uint8_t* tb, const uint32_t* pr, void* res, \
-                                           uint64_t* st, uint32_t* ef, void* s)                           \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, in, r, k, kr, mask, tb, pr, res, st, ef);                                       \
-        return run_unfor_aggregate_by_lookup<T>({false, w}, in, r, rs, {false, kw}, k, kr, krs, mask, n, lo, ns, {tb, pr, res, st}, ef, s); \
-    }                                                                                                     \
-    int fl_##S##_unfor_aggregate_by_lookup_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, \
-                                                  const uint8_t* kw, const uint64_t* ko, const T* k, size_t kb, const T* kr, size_t krs, \
-                                                  const uint32_t* mask, size_t n, T lo, uint64_t ns, const uint8_t* tb, const uint32_t* pr, \
-                                                  void* res, uint64_t* st, uint32_t* ef, void* s)         \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, w, o, pk, r, kw, ko, k, kr, mask, tb, pr, res, st, ef);                         \
-        return run_unfor_aggregate_by_lookup<T>({true, 0, w, o, pb}, pk, r, rs, {true, 0, kw, ko, kb}, k, kr, krs, mask, n, lo, ns, \
-                                                {tb, pr, res, st}, ef, s);                                \
-    }
-
-FL_DEFINE_AGGREGATE_BY_LOOKUP(uint8_t, u8)
-FL_DEFINE_AGGREGATE_BY_LOOKUP(uint16_t, u16)
-FL_DEFINE_AGGREGATE_BY_LOOKUP(uint32_t, u32)
-FL_DEFINE_AGGREGATE_BY_LOOKUP(uint64_t, u64)
-
-#define FL_DEFINE_FOR_COMPARE_RANGE(T, S)                                                               \
-    int fl_##S##_unfor_compare_range(unsigned w, const T* in, const T* r, size_t rs, T lo, T hi, int cb, const uint32_t* mi, size_t n, \
-                                     uint32_t* mask, void* s)                                             \
-    { FL_DEVICE_TIER(s, in, r, mi, mask); return run_unfor_compare_range<T>({false, w}, in, r, rs, lo, hi, cb, mi, n, mask, nullptr, s); } \
-    int fl_##S##_unfor_compare_range_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, T lo, T hi, \
-                                            int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, r, mi, mask, ef); return run_unfor_compare_range<T>({true, 0, w, o, pb}, pk, r, rs, lo, hi, cb, mi, n, mask, ef, s); }
-
-FL_DEFINE_FOR_COMPARE_RANGE(uint8_t, u8)
-FL_DEFINE_FOR_COMPARE_RANGE(uint16_t, u16)
-FL_DEFINE_FOR_COMPARE_RANGE(uint32_t, u32)
-FL_DEFINE_FOR_COMPARE_RANGE(uint64_t, u64)
-
-#define FL_DEFINE_DELTA_COMPARE_RANGE(T, S)                                                             \
-    int fl_##S##_undelta_compare_range(unsigned w, const T* in, const T* b, T lo, T hi, int cb, const uint32_t* mi, size_t n, uint32_t* mask, \
-                                       void* s)                                                           \
-    { FL_DEVICE_TIER(s, in, b, mi, mask); return run_undelta_compare_range<T>({false, w}, in, b, lo, hi, cb, mi, n, mask, nullptr, s); } \
-    int fl_##S##_undelta_compare_range_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* b, T lo, T hi, int cb, \
-                                              const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, b, mi, mask, ef); return run_undelta_compare_range<T>({true, 0, w, o, pb}, pk, b, lo, hi, cb, mi, n, mask, ef, s); }
-
-FL_DEFINE_DELTA_COMPARE_RANGE(uint8_t, u8)
-FL_DEFINE_DELTA_COMPARE_RANGE(uint16_t, u16)
-FL_DEFINE_DELTA_COMPARE_RANGE(uint32_t, u32)
-FL_DEFINE_DELTA_COMPARE_RANGE(uint64_t, u64)
-
-#define FL_DEFINE_FOR_COMPARE_IN(T, S)                                                                    \
-    int fl_##S##_unfor_compare_in(unsigned w, const T* in, const T* r, size_t rs, T lo, uint64_t sb, const uint32_t* sw, int ng, int cb, \
-                                  const uint32_t* mi, size_t n, uint32_t* mask, void* s)                  \
-    { FL_DEVICE_TIER(s, in, r, sw, mi, mask); return run_unfor_compare_in<T>({false, w}, in, r, rs, lo, sb, sw, ng, cb, mi, n, mask, nullptr, s); } \
-    int fl_##S##_unfor_compare_in_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* r, size_t rs, T lo, uint64_t sb, \
-                                         const uint32_t* sw, int ng, int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
-    { FL_DEVICE_TIER(s, w, o, pk, r, sw, mi, mask, ef); return run_unfor_compare_in<T>({true, 0, w, o, pb}, pk, r, rs, lo, sb, sw, ng, cb, mi, n, mask, ef, s); }
-
-FL_DEFINE_FOR_COMPARE_IN(uint8_t, u8)
-FL_DEFINE_FOR_COMPARE_IN(uint16_t, u16)
-FL_DEFINE_FOR_COMPARE_IN(uint32_t, u32)
-FL_DEFINE_FOR_COMPARE_IN(uint64_t, u64)
-
-#define FL_DEFINE_FOR_COMPARE_COLUMNS(T, S)                                                               \
-    int fl_##S##_unfor_compare_columns(unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, size_t brs, \
-                                       int op, int sg, int cb, const uint32_t* mi, size_t n, uint32_t* mask, void* s) \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, a, ar, b, br, mi, mask);                                                        \
-        return run_unfor_compare_columns<T>({false, wa}, a, ar, ars, {false, wb}, b, br, brs, op, sg, cb, mi, n, mask, nullptr, s); \
-    }                                                                                                     \
-    int fl_##S##_unfor_compare_columns_widths(const uint8_t* aw, const uint64_t* ao, const T* a, size_t ab, const T* ar, size_t ars, \
-                                              const uint8_t* bw, const uint64_t* bo, const T* b, size_t bb, const T* br, size_t brs, \
-                                              int op, int sg, int cb, const uint32_t* mi, size_t n, uint32_t* mask, uint32_t* ef, void* s) \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, aw, ao, a, ar, bw, bo, b, br, mi, mask, ef);                                    \
-        return run_unfor_compare_columns<T>({true, 0, aw, ao, ab}, a, ar, ars, {true, 0, bw, bo, bb}, b, br, brs, op, sg, cb, mi, n, mask, ef, s); \
-    }
-
-FL_DEFINE_FOR_COMPARE_COLUMNS(uint8_t, u8)
-FL_DEFINE_FOR_COMPARE_COLUMNS(uint16_t, u16)
-FL_DEFINE_FOR_COMPARE_COLUMNS(uint32_t, u32)
-FL_DEFINE_FOR_COMPARE_COLUMNS(uint64_t, u64)
-
-#define FL_DEFINE_AGGREGATE_COLUMNS(T, S)                                                                 \
-    int fl_##S##_unfor_aggregate_columns(int ex, unsigned wa, const T* a, const T* ar, size_t ars, unsigned wb, const T* b, const T* br, \
-                                         size_t brs, const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, void* s) \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, a, ar, b, br, mask, aggs, ef);                                                  \
-        return run_unfor_aggregate_columns<T>(ex, {false, wa}, a, ar, ars, {false, wb}, b, br, brs, mask, n, aggs, ef, s); \
-    }                                                                                                     \
-    int fl_##S##_unfor_aggregate_columns_widths(int ex, const uint8_t* aw, const uint64_t* ao, const T* a, size_t ab, const T* ar, size_t ars, \
-                                                const uint8_t* bw, const uint64_t* bo, const T* b, size_t bb, const T* br, size_t brs, \
-                                                const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, void* s) \
-    {                                                                                                     \
-        FL_DEVICE_TIER(s, aw, ao, a, ar, bw, bo, b, br, mask, aggs, ef);                                  \
-        return run_unfor_aggregate_columns<T>(ex, {true, 0, aw, ao, ab}, a, ar, ars, {true, 0, bw, bo, bb}, b, br, brs, mask, n, aggs, ef, s); \
-    }
-
-FL_DEFINE_AGGREGATE_COLUMNS(uint8_t, u8)
-FL_DEFINE_AGGREGATE_COLUMNS(uint16_t, u16)
-FL_DEFINE_AGGREGATE_COLUMNS(uint32_t, u32)
-FL_DEFINE_AGGREGATE_COLUMNS(uint64_t, u64)
-
-FL_DEFINE_TYPE(uint8_t, u8)
-FL_DEFINE_TYPE(uint16_t, u16)
-FL_DEFINE_TYPE(uint32_t, u32)
-FL_DEFINE_TYPE(uint64_t, u64)
+FL_FOR_EACH_TYPE(FL_DEFINE_TYPE)
 
 
 // ---- fl_internal_*: the hooks of the tests and the A/B tools (include/fastlanes_amd_internal.h), not part of the stable ABI ----------

@@ -1,5 +1,5 @@
 // fl_host.hpp -- host-side helpers shared by the C ABI's two translation units: fl_capi.hip (the codec boundary, with the host tier of
-// fl_host_tier.hpp) and fl_pair.hip
+// fl_host_tier.hpp, the scans of fl_scan.hpp and the consumers of a packed column of fl_consumer_tier.hpp) and fl_pair.hip
 // (fl_column_pair_alloc / _free and what stands behind them).  No kernels.  FL_DEVICE_TIER also needs fl_kernels.hpp, which both include.
 #pragma once
 #include "../../include/fastlanes_amd.h"

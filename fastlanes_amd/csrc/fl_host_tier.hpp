@@ -1,5 +1,6 @@
 // fl_host_tier.hpp -- the host tier of the C ABI (fl_<ty>_*_host, fl_host_release): the per-thread context, its staging buffers and the
-// zero-copy completion word.  Included by exactly one translation unit of the library (fl_capi.hip), as fl_scan.hpp is: k_host_done
+// zero-copy completion word.  Included by exactly one translation unit of the library (fl_capi.hip), as fl_scan.hpp and
+// fl_consumer_tier.hpp are: k_host_done
 // below is part of that file's code object, and host_unpack_single calls its dev_unpack_single (declared here, defined there).
 #pragma once
 #include "fl_host.hpp"

@@ -140,6 +140,37 @@ def test_uniform_width_form(fl, oracle, ty):
 
 
 @pytest.mark.parametrize("ty", TYS)
+def test_three_blocks_unlike_widths_and_strides_in_both_forms(fl, oracle, ty):
+    """3 blocks, column a of width 5 against column b of width 3, one reference per block on one side and one broadcast reference on
+    the other (then the other way round), a - b (which tells a from b) and a * b, through the uniform-width form and the mixed-width
+    one.  The broadcast reference is the head of a longer tensor: a stride of 1 where 0 is meant reads other references, a column or a
+    stride in the other's place changes the slots."""
+    import torch
+    T, n = tbits(ty), 3
+    apk, bpk = values(ty, n * packed_len(ty, 5), 20100 + T), values(ty, n * packed_len(ty, 3), 20101 + T)
+    ra, rb = values(ty, n, 20102 + T), values(ty, n, 20103 + T)
+    assert len(set(ra.tolist())) == n and len(set(rb.tolist())) == n
+    dapk, dbpk, dra, drb = to_dev(apk), to_dev(bpk), to_dev(ra), to_dev(rb)
+    daw, dbw = (torch.full((n,), w, dtype=torch.uint8, device="cuda:0") for w in (5, 3))
+    daoff, dboff = fl.widths_to_offsets(ty, daw)[0], fl.widths_to_offsets(ty, dbw)[0]
+    bits = np.random.default_rng(20104 + T).random(n * 1024) < 0.6
+    dm = mask_words(bits)
+    for a_broadcast in (False, True):
+        ha, hb = (np.full(n, ra[0]), rb) if a_broadcast else (ra, np.full(n, rb[0]))
+        fa, fb = (dra[:1], drb) if a_broadcast else (dra, drb[:1])
+        va = oracle.batch("unfor_pack", ty, 5, apk, aux=ha, n_blocks=n)
+        vb = oracle.batch("unfor_pack", ty, 3, bpk, aux=hb, n_blocks=n)
+        for op in ("-", "*"):
+            want = expected_blocks(expr(op, va, vb), bits)
+            buf, slots = sentinel_slots(n)
+            result, _ = fl.FoR.unfor_aggregate_columns(5, dapk, fa, op, 3, dbpk, fb, mask=dm, n_blocks=n, block_aggs=slots)
+            check_slots(buf, n, result, want, (ty, a_broadcast, op, "uniform"))
+            buf, slots = sentinel_slots(n)
+            result, _ = fl.unfor_aggregate_columns_widths(daw, daoff, dapk, fa, op, dbw, dboff, dbpk, fb, mask=dm, block_aggs=slots)
+            check_slots(buf, n, result, want, (ty, a_broadcast, op, "mixed"))
+
+
+@pytest.mark.parametrize("ty", TYS)
 def test_consistent_with_the_shipped_aggregate(fl, oracle, ty):
     """A constant column b (width 0 in every block, no packed bytes): a * 1 and a + 0 equal unfor_aggregate_widths of column a, slot for
     slot; a - a is {count, 0, 0, 0} on every block that keeps something"""

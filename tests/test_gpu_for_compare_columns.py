@@ -233,6 +233,37 @@ def test_uniform_width_every_width_pair(fl, oracle, ty):
 
 
 @pytest.mark.parametrize("ty", TYS)
+def test_three_blocks_unlike_widths_and_strides_in_both_forms(fl, oracle, ty):
+    """3 blocks, column a of width 5 against column b of width 3, one reference per block on one side and one broadcast reference on
+    the other (then the other way round), all six ops -- those the entry point serves by swapping the columns among them -- through the
+    uniform-width form and the mixed-width one.  The broadcast reference is the head of a longer tensor: a stride of 1 where 0 is meant
+    reads other references, a column or a stride in the other's place changes the mask."""
+    import torch
+    T, n = tbits(ty), 3
+    apk, bpk = values(ty, n * packed_len(ty, 5), 12400 + T), values(ty, n * packed_len(ty, 3), 12401 + T)
+    r = int(values(ty, 1, 12402 + T)[0])                                    # every pair of ranges overlaps, whichever references meet
+    ra, rb = (np.array([(r + d) % (1 << T) for d in ds], dtype=TYPES[ty][0]) for ds in ((0, 4, 8), (6, 12, 2)))
+    dapk, dbpk, dra, drb = to_dev(apk), to_dev(bpk), to_dev(ra), to_dev(rb)
+    daw, dbw = (torch.full((n,), w, dtype=torch.uint8, device="cuda:0") for w in (5, 3))
+    daoff, dboff = fl.widths_to_offsets(ty, daw)[0], fl.widths_to_offsets(ty, dbw)[0]
+    min_host = incoming_mask(n, 12403 + T)
+    dmin = to_dev(min_host)
+    for a_broadcast in (False, True):
+        ha, hb = (np.full(n, ra[0]), rb) if a_broadcast else (ra, np.full(n, rb[0]))
+        fa, fb = (dra[:1], drb) if a_broadcast else (dra, drb[:1])
+        va = oracle.batch("unfor_pack", ty, 5, apk, aux=ha, n_blocks=n)
+        vb = oracle.batch("unfor_pack", ty, 3, bpk, aux=hb, n_blocks=n)
+        for i, op in enumerate(OPS):
+            signed, cb = bool(i % 2), COMBINE[i % 3]
+            want = want_mask(va, vb, op, signed, cb, min_host)
+            args = dict(mask=dmin, combine=cb) if cb != "new" else {}
+            got = got_mask(fl.FoR.unfor_compare_columns(5, dapk, fa, op, 3, dbpk, fb, signed=signed, n_blocks=n, output=prefilled(n), **args))
+            assert np.array_equal(got, want), (ty, a_broadcast, op, signed, cb, "uniform")
+            got = got_mask(fl.unfor_compare_columns_widths(daw, daoff, dapk, fa, op, dbw, dboff, dbpk, fb, signed=signed, output=prefilled(n), **args))
+            assert np.array_equal(got, want), (ty, a_broadcast, op, signed, cb, "mixed")
+
+
+@pytest.mark.parametrize("ty", TYS)
 def test_device_checks_on_both_columns(fl, oracle, ty):
     """A width > T in column a (block 7), a misaligned offset in column b (block 5), a block outside the packed bytes in both (block
     11): err_flag holds the three bits, the three blocks keep their prefill, every other block is right under each combiner, and

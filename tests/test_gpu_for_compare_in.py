@@ -233,6 +233,31 @@ def test_mixed_column_outside_every_window_and_empty_columns(fl, oracle, ty):
         fl.unfor_compare_in_widths(dw, doff, dcol, drefs, fl.member_set(other, [1, 2]))
 
 
+@pytest.mark.parametrize("ty", TYS)
+def test_an_empty_set_never_looks_at_its_words(fl, ty):
+    """set_bits == 0 through the C ABI, both forms, 3 blocks: set_words is deliberately NOT NULL and NOT 16-byte aligned (4 bytes into a
+    live allocation).  The call must be accepted and answer for the empty set: no row is a member, every row is under negate."""
+    import ctypes
+    import torch
+    T, n, w = tbits(ty), 3, 5
+    dpk, drefs = to_dev(values(ty, n * packed_len(ty, w), 43100 + T)), to_dev(values(ty, n, 43101 + T))
+    dw = torch.full((n,), w, dtype=torch.uint8, device="cuda:0")
+    doff, _ = fl.widths_to_offsets(ty, dw)
+    live = torch.full((64,), PREFILL, dtype=torch.int32, device="cuda:0")
+    odd = live.data_ptr() + 4
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib = fl.load()
+    for negate in (0, 1):
+        mask, err = prefilled(n), torch.zeros(1, dtype=torch.int32, device="cuda:0")
+        rc = getattr(lib, f"fl_{ty}_unfor_compare_in")(w, dpk.data_ptr(), drefs.data_ptr(), 1, 17, 0, odd, negate, 0, None, n, mask.data_ptr(), stream)
+        assert rc == 0 and (got_mask(mask) == -negate).all(), (ty, negate, rc, "uniform")
+        mask = prefilled(n)
+        rc = getattr(lib, f"fl_{ty}_unfor_compare_in_widths")(dw.data_ptr(), doff.data_ptr(), dpk.data_ptr(), dpk.numel() * (T // 8), drefs.data_ptr(), 1,
+                                                              17, 0, odd, negate, 0, None, n, mask.data_ptr(), err.data_ptr(), stream)
+        assert rc == 0 and int(err.item()) == 0 and (got_mask(mask) == -negate).all(), (ty, negate, rc, "mixed")
+    assert (live.cpu().numpy() == PREFILL).all()
+
+
 def test_chain_in_and_between_then_aggregate(fl):
     """WHERE mode IN (1, 4, 6) AND ts BETWEEN a AND b, then COUNT / SUM / MIN / MAX of z: three small columns of different types
     through the library's own encoder, the second predicate chained in place through the first one's mask, against numpy."""

@@ -197,6 +197,35 @@ def test_output_bounds_never_write_outside(fl, oracle, ty):
     assert ei.value.status == 6
 
 
+@pytest.mark.parametrize("ty", TYS)
+def test_uniform_width_form_raises_its_error_flag(fl, oracle, ty):
+    """The uniform-width entry point takes an err_flag too, alone among the consumers' uniform forms: 3 blocks with out_len one short of
+    the total raise FL_DEVERR_BOUNDS in it and skip exactly the last block; with out_len right the flag stays 0."""
+    import torch
+    T, n, w = tbits(ty), 3, 5
+    pk, refs = values(ty, n * packed_len(ty, w), 15100 + T), values(ty, n, 15101 + T)
+    vals = oracle.batch("unfor_pack", ty, w, pk, aux=refs, n_blocks=n)
+    bits = np.random.default_rng(15102 + T).random(n * 1024) < 0.3
+    dm = mask_words(bits)
+    oo, _ = fl.mask_offsets(dm)
+    total, start_last = int(bits.sum()), int(bits[:(n - 1) * 1024].sum())
+    assert start_last < total
+    dpk, drefs = to_dev(pk), to_dev(refs)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for out_len, flag in ((total, 0), (total - 1, 8)):
+        want = vals[bits].copy()
+        if flag:
+            want[start_last:] = sentinel_of(ty)                    # the overflowing block's slots stay as they were
+        buf = sentinel_buffer(ty, total + GUARD)
+        err = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+        rc = getattr(fl.load(), f"fl_{ty}_unfor_select")(w, dpk.data_ptr(), drefs.data_ptr(), 1, dm.data_ptr(), oo.data_ptr(), buf.data_ptr(), out_len,
+                                                         n, err.data_ptr(), stream)
+        assert rc == 0 and int(err.item()) == flag, (ty, out_len, rc, int(err.item()))
+        got = to_np(buf, ty)
+        assert np.array_equal(got[:total], want), (ty, out_len)
+        assert (got[total:] == sentinel_of(ty)).all(), (ty, out_len, "the guard was written")
+
+
 @pytest.mark.parametrize("policy", POLICIES + [8 << 25, 12 << 25, 31 << 25, 2 + (8 << 25)])
 @pytest.mark.parametrize("ty", TYS)
 def test_policies_windows_streams_and_empty_columns(fl, oracle, kernel_policy, ty, policy):
