@@ -30,7 +30,7 @@ def _ptr(*types):
     return [ctypes.POINTER(t) for t in types]
 
 
-# THE table of the C ABI: (header macro group, symbol, restype, argtypes), in header order.  A symbol with "{ty}" (or "{vty}") is declared once per
+# THE table of the C ABI: (header macro group, symbol, restype, argtypes), in header order.  A symbol with "{ty}" (or "{vty}", "{dty}") is declared once per
 # element type by its group's FL_DECLARE_* macro (_T in its argtypes is that type's scalar); the groups "API" (include/fastlanes_amd.h)
 # and "INTERNAL" (include/fastlanes_amd_internal.h: test / measurement hooks, not part of the stable ABI) are plain prototypes.
 # argtypes None: left unset.  Every symbol list below, and load(), is derived from it.
@@ -167,6 +167,10 @@ _SIGNATURES = (
     # above)
     ("DELTA_COMPARE_RANGE", "fl_{vty}_undelta_compare_range", _I, [_U, _P, _P, _T, _T, _I, _P, _Z, _P, _P]),
     ("DELTA_COMPARE_RANGE", "fl_{vty}_undelta_compare_range_widths", _I, [_P, _P, _P, _Z, _P, _T, _T, _I, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_DELTA_AGGREGATE (device tier): count / sum / min / max per block of the rows a mask keeps of a DELTA-packed column
+    # ({dty}: the element type of the Delta column; these rows' refusals are recorded by tests/test_delta_aggregate_cpu.py)
+    ("DELTA_AGGREGATE", "fl_{dty}_undelta_aggregate", _I, [_U, _P, _P, _P, _Z, _P, _P, _P]),
+    ("DELTA_AGGREGATE", "fl_{dty}_undelta_aggregate_widths", _I, [_P, _P, _P, _Z, _P, _P, _Z, _P, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -178,9 +182,9 @@ def _rows(*groups):
     for every element type -- all of u8's symbols, then u16's, ... as the header's macros expand."""
     for group in groups or dict.fromkeys(g for g, *_ in _SIGNATURES):
         rows = [r for r in _SIGNATURES if r[0] == group]
-        for ty in TYPES if "{ty}" in rows[0][1] or "{vty}" in rows[0][1] else (None,):
+        for ty in TYPES if any(t in rows[0][1] for t in ("{ty}", "{vty}", "{dty}")) else (None,):
             for _, name, restype, argtypes in rows:
-                yield name.format(ty=ty, vty=ty), restype, argtypes and [CTYPE[ty] if a is _T else a for a in argtypes]
+                yield name.format(ty=ty, vty=ty, dty=ty), restype, argtypes and [CTYPE[ty] if a is _T else a for a in argtypes]
 
 
 def _symbols(*groups):
@@ -270,6 +274,12 @@ def delta_compare_range_symbols():
     """The symbols FL_DECLARE_DELTA_COMPARE_RANGE declares: for all four element types the interval predicate over a uniform-width and
     over a mixed-width Delta-packed column."""
     return _symbols("DELTA_COMPARE_RANGE")
+
+
+def delta_aggregate_symbols():
+    """The symbols FL_DECLARE_DELTA_AGGREGATE declares: for all four element types the aggregate over a uniform-width and over a
+    mixed-width Delta-packed column."""
+    return _symbols("DELTA_AGGREGATE")
 
 
 _LIB = None

@@ -839,6 +839,26 @@ class Delta:
         return out
 
     @staticmethod
+    def undelta_aggregate(width, packed, base, mask=None, n_blocks=None, block_aggs=None, check=True):
+        """COUNT / SUM / MIN / MAX straight from a Delta-packed column: of the values Delta.undelta_pack_untranspose(width, packed, base)
+        yields (ORIGINAL row order) where `mask` (the layout every compare writes and undelta_compare_range returns: a CUDA int32 tensor of
+        32 words per block, bit i = original row i) has a 1 -- `mask=None`: of every value, and no mask is read -- without materialising
+        them.  Returns (result, block_aggs) exactly as FoR.unfor_aggregate does: uint64 bit patterns count, sum (wrapping mod 2^64), min,
+        max; nothing kept gives (0, 0, 2^64 - 1, 0).  `base` holds LANES = 1024/T elements per block.  A block whose mask is empty, or
+        whose width is 0 (each lane's rows repeat its base), reads no packed byte.  Device tier only; no host round trip (`check` only
+        matters for the mixed-width form).  n_blocks is only needed for width == 0 (default: from `base`)."""
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("undelta_aggregate is device tier (pass CUDA tensors)")
+        lanes = 1024 // _lib.BITS[ty]
+        if n_blocks is None and width == 0:
+            n_blocks = _numel(base) // lanes
+        n = _uniform_blocks(src, width, "undelta_aggregate", n_blocks, (mask if _is_torch(mask) else None, 32))
+        b, _ = _block_bases(src, ty, base, n)
+        return _aggregate_call(f"fl_{ty}_undelta_aggregate", src, n, (width, src.ptr, b.ptr), mask, block_aggs, check)
+
+    @staticmethod
     def transpose_delta_pack(width, input, base, output=None):
         """== BitPacking.pack(width, Delta.delta(Transpose.transpose(input), base)): encodes straight
         from the ORIGINAL element order.  Device tier only."""
@@ -1679,7 +1699,7 @@ def _aggregate_call(name, src, n, lead, mask, block_aggs, check):
     if block_aggs is None:
         slots = torch.empty((n, 4), dtype=torch.int64, device=dev)
     else:
-        slots = _consumer_out(src, block_aggs, torch.int64, n * 4, name[name.index("unfor"):]).view(n, 4)
+        slots = _consumer_out(src, block_aggs, torch.int64, n * 4, name.split("_", 2)[2]).view(n, 4)
     flag = _Flag(check, dev)
     _launch(name, dev, *lead, m.ptr if m is not None and n else None, n, slots.data_ptr() if n else None, flag.ptr)
     result = aggregate_reduce(slots)        # enqueued before the flag is read back: the sync below covers both launches
@@ -1849,6 +1869,20 @@ def undelta_compare_range_widths(widths, offsets, packed, base, lo, hi, mask=Non
             m.ptr if m is not None and n else None, n, out.data_ptr(), flag.ptr)
     flag.raise_if_set(f"fl_{ty}_undelta_compare_range_widths")  # bitpacking.rs:93,126 unreachable!(); :111-113
     return out
+
+
+def undelta_aggregate_widths(widths, offsets, packed, base, mask=None, block_aggs=None, check=True):
+    """Delta.undelta_aggregate over a mixed-width column: COUNT / SUM / MIN / MAX of the values undelta_pack_widths(widths, offsets, packed,
+    base, untranspose=True) yields where `mask` (32 words per block, bit i = original row i; None: everywhere) has a 1.  Returns (result,
+    block_aggs) as FoR.unfor_aggregate does; the mask of undelta_compare_range_widths chains straight into it.  The per-block device
+    checks of unfor_pack_widths, with unfor_aggregate_widths' contract: a block that fails them is skipped and ITS SLOT HOLDS THE IDENTITY
+    (0, 0, 2^64 - 1, 0), so `result` combines the valid blocks; `check=True` reads the device error flag back (one sync) and raises,
+    `check=False` stays asynchronous."""
+    src = _Arg(packed)
+    ty = src.ty
+    n, lead = _widths_column("undelta_aggregate_widths", src, widths, offsets)
+    b, aux = _block_bases(src, ty, base, n)
+    return _aggregate_call(f"fl_{ty}_undelta_aggregate_widths", src, n, (*lead, *aux), mask, block_aggs, check)
 
 
 def transpose_delta_pack_widths(widths, offsets, input, base, output, check=True):

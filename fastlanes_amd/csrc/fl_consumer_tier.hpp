@@ -1,9 +1,9 @@
 // fl_consumer_tier.hpp -- the host side of the consumers of a packed column (fl_for_block.hpp), and their extern "C" entry points:
 // unfor_compare, _compare_range, _compare_in, _compare_columns, _select, _aggregate, _aggregate_columns, _aggregate_by,
 // _aggregate_by_columns, _aggregate_by_window, _aggregate_by_lookup, _set_build, _lookup (and _lookup_u8) over a FoR-packed column,
-// undelta_compare_range over a Delta-packed one.  Included by exactly one translation unit of the library (fl_capi.hip), as
+// undelta_compare_range and undelta_aggregate over a Delta-packed one.  Included by exactly one translation unit of the library (fl_capi.hip), as
 // fl_host_tier.hpp and fl_scan.hpp are, below that file's Column, WaveShape, with_policy, widths_args, no_bytes and FL_FOR_EACH_TYPE.
-// In this order: the column value; the refusal steps, once each; the repeated parts of the argument blocks, once each; the fourteen
+// In this order: the column value; the refusal steps, once each; the repeated parts of the argument blocks, once each; the fifteen
 // run_*, each composing the steps top to bottom in ITS order -- the status of a call with two faults depends on it, and
 // tests/test_cabi_refusals_cpu.py records it; extern "C".
 #pragma once
@@ -13,6 +13,7 @@
 #include "fl_for_compare_in.hpp"
 #include "fl_for_compare_columns.hpp"
 #include "fl_delta_compare_range.hpp"
+#include "fl_delta_aggregate.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_columns.hpp"
@@ -29,7 +30,7 @@ using namespace fl;
 
 // One packed column of a consumer: uniform-width (form.width, blocks back to back) or mixed-width (widths[] / offsets[], checked per
 // block by the kernel).  refs: FoR's references, block b's at refs[b * ref_stride] (stride 1: one per block, 0: one for the column)
-// -- or, for undelta_compare_range, Delta's bases, with stride 0.  All columns of one call have one form.
+// -- or, for undelta_compare_range and undelta_aggregate, Delta's bases, with stride 0.  All columns of one call have one form.
 template <typename T> struct PackedColumn {
     Column form;
     const T* packed;
@@ -261,6 +262,27 @@ int run_unfor_aggregate(PackedColumn<T> col, const uint32_t* mask, size_t n_bloc
     a.aggs = static_cast<char*>(block_aggs);
     a.agg_refs = col.refs;
     return hip_status(aggregate_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// undelta_aggregate (fl_delta_aggregate.hpp): unfor_aggregate over a Delta-packed column -- col.refs are the bases (LANES per block, 128
+// bytes, read as 16-byte cells), required and aligned; a block that fails the kernel's checks leaves the identity in its slot; `mask` may
+// be NULL.  One block per wavefront for every type, at unfor_pack_widths' occupancy.  Order (unfor_aggregate's): width; the empty
+// column; the column, its bases and `block_aggs`; alignment.
+template <typename T>
+int run_undelta_aggregate(PackedColumn<T> col, const uint32_t* mask, size_t n_blocks, void* block_aggs, uint32_t* err_flag, void* stream)
+{
+    if (any_over_width(col)) return FL_ERR_WIDTH;
+    if (n_blocks == 0) return FL_OK;
+    if (!columns_present(col) || !block_aggs) return FL_ERR_NULL;
+    if (any_misaligned(col.packed, col.refs, mask, block_aggs)) return FL_ERR_ALIGN;
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), 1u, 0u});
+    DeltaAggregateArgs a;
+    column_args<T>(a, col, n_blocks, err_flag, sh);
+    a.mask = mask;
+    a.aggs = static_cast<char*>(block_aggs);
+    a.agg_refs = nullptr;
+    a.bases = reinterpret_cast<const char*>(col.refs);
+    return hip_status(delta_aggregate_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // unfor_aggregate_columns (fl_aggregate_columns.hpp): two columns of T met element by element under `expr` and aggregated per block as
@@ -592,6 +614,18 @@ FL_FOR_EACH_TYPE(FL_DEFINE_SELECT)
     int fl_##S##_unfor_aggregate_widths(FL_MIXED_PARAMS(T, ), const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, void* s)     \
     { FL_DEVICE_TIER(s, w, o, pk, r, mask, aggs, ef); return run_unfor_aggregate<T>(FL_MIXED(T, ), mask, n, aggs, ef, s); }
 FL_FOR_EACH_TYPE(FL_DEFINE_AGGREGATE)
+
+// Delta's bases stand where the references stood, with stride 0
+#define FL_DEFINE_DELTA_AGGREGATE(T, S)                                                                                              \
+    int fl_##S##_undelta_aggregate(unsigned w, const T* pk, const T* b, const uint32_t* mask, size_t n, void* aggs, uint32_t* ef, void* s) \
+    { FL_DEVICE_TIER(s, pk, b, mask, aggs, ef); return run_undelta_aggregate<T>(uniform_column<T>(w, pk, b, 0), mask, n, aggs, ef, s); } \
+    int fl_##S##_undelta_aggregate_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* b, const uint32_t* mask, \
+                                          size_t n, void* aggs, uint32_t* ef, void* s)                                               \
+    {                                                                                                                                \
+        FL_DEVICE_TIER(s, w, o, pk, b, mask, aggs, ef);                                                                              \
+        return run_undelta_aggregate<T>(mixed_column<T>(w, o, pk, pb, b, 0), mask, n, aggs, ef, s);                                  \
+    }
+FL_FOR_EACH_TYPE(FL_DEFINE_DELTA_AGGREGATE)
 
 #define FL_DEFINE_AGGREGATE_COLUMNS(T, S)                                                                                            \
     int fl_##S##_unfor_aggregate_columns(int ex, FL_UNIFORM_PARAMS(T, a), FL_UNIFORM_PARAMS(T, b), const uint32_t* mask, size_t n,   \

@@ -20,6 +20,7 @@
 //   24 unfor_lookup (a dimension attribute of the key's own type or u8 fetched through such a column inside a dense window of the key domain under a mask, written in full-width packed order: the probe side of a payload join; fl_lookup.hpp)
 //   25 unfor_aggregate_by_lookup (count / sum / min / max per u8 attribute fetched through a key column inside a dense window of the key domain, value and key column FoR-packed and of one type: unfor_lookup_u8 and unfor_aggregate_by in one pass with no per-row output; fl_aggregate_by_lookup.hpp)
 //   26 undelta_compare_range (an interval predicate over a Delta-packed column, joined with the mask so far: the chains are decoded in place of the rows, no value is untransposed, a block its bases decide reads no packed byte; fl_delta_compare_range.hpp)
+//   27 undelta_aggregate (count / sum / min / max per block of the rows a mask keeps of a Delta-packed column: the chains are aggregated where they are decoded, each under its T-bit group of the mask, no value is untransposed, an empty-mask or width-0 block reads no packed byte; fl_delta_aggregate.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -40,6 +41,7 @@
 #include "fl_lookup.hpp"
 #include "fl_aggregate_by_lookup.hpp"
 #include "fl_delta_compare_range.hpp"
+#include "fl_delta_aggregate.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -201,7 +203,9 @@ template <> lookup_launch_t lookup_launcher<T>(unsigned payload_bytes, int tier)
 template <> aggregate_by_lookup_launch_t aggregate_by_lookup_launcher<T>() { return &launch_aggregate_by_lookup<T>; }
 #elif FL_FAMILY == 26
 template <> delta_range_launch_t delta_range_launcher<T>() { return &launch_block_consumer<T, DeltaRangeArgs, k_undelta_compare_range<T>, false>; }
+#elif FL_FAMILY == 27
+template <> delta_aggregate_launch_t delta_aggregate_launcher<T>() { return &launch_block_consumer<T, DeltaAggregateArgs, k_undelta_aggregate<T>, false>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..26"
+#error "FL_FAMILY must be 0..6 or 8..27"
 #endif
 }  // namespace fl

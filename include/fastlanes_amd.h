@@ -486,7 +486,7 @@ FL_DECLARE_SELECT(uint64_t, u64)
  * An empty V_b gives the IDENTITY {0, 0, UINT64_MAX, 0} of
  *     combine(a, b) = { a.count + b.count, a.sum + b.sum (wrapping), min(a.min, b.min), max(a.max, b.max) }.
  * mask == NULL keeps every row, and no mask is read.  reference_stride 0 broadcasts references[0]; one zero reference with stride 0
- * aggregates a plain bit-packed column.  Delta columns are out of scope, as for select.  Two steps, both asynchronous on `stream`, no
+ * aggregates a plain bit-packed column.  A Delta-packed column has fl_<ty>_undelta_aggregate (below).  Two steps, both asynchronous on `stream`, no
  * allocation, no synchronisation:
  *   1. fl_<ty>_unfor_aggregate / fl_<ty>_unfor_aggregate_widths: block_aggs[b] = agg_b for EVERY block (a device array of n_blocks
  *      fl_block_aggregate, 32 bytes each) -- a result in its own right: per-chunk aggregates, zone maps.  A block whose mask is empty,
@@ -1047,7 +1047,8 @@ FL_DECLARE_AGGREGATE_BY_LOOKUP(uint64_t, u64)
  * width > T is FL_ERR_WIDTH (also for an empty column); a `combine` outside the enum FL_ERR_INDEX; n_blocks == 0 FL_OK; mask_in ==
  * NULL with AND / OR, or any other required pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only when no byte can be read:
  * width 0, or packed_bytes == 0); the packed column, `bases`, `mask` and `mask_in` are 16-byte aligned (FL_ERR_ALIGN).
- * Out of scope: masks in transposed order; Delta forms of select and the aggregates; the host tier.
+ * Out of scope: masks in transposed order; the Delta form of select and the grouped Delta aggregates (fl_<ty>_undelta_aggregate, below,
+ * aggregates one Delta column under such a mask); the host tier.
  * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
  * are pinned surfaces.)
  */
@@ -1064,6 +1065,46 @@ FL_DECLARE_DELTA_COMPARE_RANGE(uint8_t, u8)
 FL_DECLARE_DELTA_COMPARE_RANGE(uint16_t, u16)
 FL_DECLARE_DELTA_COMPARE_RANGE(uint32_t, u32)
 FL_DECLARE_DELTA_COMPARE_RANGE(uint64_t, u64)
+
+/*
+ * EXTENSION: COUNT / SUM / MIN / MAX OF A DELTA-PACKED COLUMN, uniform or mixed width, over the rows a selection mask
+ * keeps -- SELECT COUNT(*), MIN(ts), MAX(ts), SUM(ts) WHERE sensor = 3 AND ts BETWEEN a AND b on the sorted or nearly sorted columns a
+ * FastLanes writer stores Delta-coded, and their per-block zone maps -- with no decoded column written or read back.  Defined as the
+ * composition (arithmetic mod 2^T unless stated)
+ *     v[b]  = untranspose(undelta_pack::<W_b>(block b, bases[b*LANES .. b*LANES + LANES]))        (delta.rs:47-63, transpose.rs:17-22)
+ *     V_b   = [ v[b][i]  for i if bit i of block b of mask ]          mask == NULL: every i, and no mask is read
+ *     agg_b = { count = |V_b|, sum = sum of V_b zero-extended to u64 (wrapping mod 2^64), min = min V_b, max = max V_b }
+ *             nothing kept: the identity {0, 0, UINT64_MAX, 0}
+ * The mask is the one every compare entry point writes and fl_<ty>_undelta_compare_range produces: 32 words per block, bit i = the
+ * ORIGINAL row i, LSB first.  block_aggs[b] = agg_b for EVERY block (fl_block_aggregate, 32 bytes each); the reduction to one result is
+ * fl_aggregate_reduce, and everything about slots, identity and determinism is fl_<ty>_unfor_aggregate's.  `bases` holds LANES =
+ * 1024 / T elements per block (128 bytes), as for fl_<ty>_undelta_pack.
+ * A block whose mask is empty, and a block of width 0 (each lane's T rows repeat its base: count = sum of p_l, sum = sum of p_l * base_l
+ * with p_l the kept rows of lane l, min / max over the lanes with p_l > 0), read no packed byte.  The mixed-width form runs the per-block
+ * device checks of fl_<ty>_unfor_pack_widths: a failing block raises its FL_DEVERR_* bit in *err_flag and ITS SLOT RECEIVES THE IDENTITY
+ * (the aggregate's contract, not the compare's "left untouched").  err_flag follows fl_<ty>_unfor_aggregate[_widths]' rule.  Device
+ * tier, asynchronous on `stream`; allocates nothing, uses no scratch memory.
+ * width > T is FL_ERR_WIDTH (also for an empty column); n_blocks == 0 FL_OK; a required pointer NULL FL_ERR_NULL (`bases` is required;
+ * `in` / `packed` may be NULL only when no byte can be read: width 0, or packed_bytes == 0); the packed column, `bases`, `mask` and
+ * `block_aggs` are 16-byte aligned (FL_ERR_ALIGN).
+ * Out of scope: the Delta form of select (it needs original-order compaction), grouped or two-column Delta aggregates, masks in
+ * transposed order, signed columns, the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_DELTA_AGGREGATE(T, S)                                                                  \
+    int fl_##S##_undelta_aggregate(unsigned width, const T *in, const T *bases,                           \
+                                   const uint32_t *mask /* may be NULL */, size_t n_blocks,               \
+                                   void *block_aggs, uint32_t *err_flag, void *stream);                   \
+    int fl_##S##_undelta_aggregate_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed, \
+                                          size_t packed_bytes, const T *bases,                            \
+                                          const uint32_t *mask /* may be NULL */, size_t n_blocks,        \
+                                          void *block_aggs, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_DELTA_AGGREGATE(uint8_t, u8)
+FL_DECLARE_DELTA_AGGREGATE(uint16_t, u16)
+FL_DECLARE_DELTA_AGGREGATE(uint32_t, u32)
+FL_DECLARE_DELTA_AGGREGATE(uint64_t, u64)
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,8 @@ template <typename T> struct Abi;
         static constexpr auto unfor_aggregate_by_lookup_widths = fl_##S##_unfor_aggregate_by_lookup_widths; \
         static constexpr auto undelta_compare_range = fl_##S##_undelta_compare_range;                \
         static constexpr auto undelta_compare_range_widths = fl_##S##_undelta_compare_range_widths;  \
+        static constexpr auto undelta_aggregate = fl_##S##_undelta_aggregate;                        \
+        static constexpr auto undelta_aggregate_widths = fl_##S##_undelta_aggregate_widths;          \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -347,6 +349,11 @@ template <typename T> struct Delta : BitPacking<T> {
     static void undelta_compare_range_device(std::size_t width, const T* d_packed, const T* d_bases, T lo, T hi, fl_mask_combine combine,
                                              const std::uint32_t* d_mask_in, std::size_t n_blocks, std::uint32_t* d_mask, void* stream = nullptr)
     { detail::check(A::undelta_compare_range((unsigned)width, d_packed, d_bases, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, stream), "undelta_compare_range_device"); }
+    // COUNT / SUM / MIN / MAX per block of the rows d_mask keeps (nullptr: every row) of the Delta-packed column, in original row order:
+    // d_block_aggs[b] as FoR<T>::unfor_aggregate_device writes it, reduced by aggregate_reduce_device; no decoded column is written
+    static void undelta_aggregate_device(std::size_t width, const T* d_packed, const T* d_bases, const std::uint32_t* d_mask, std::size_t n_blocks,
+                                         fl_block_aggregate* d_block_aggs, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::undelta_aggregate((unsigned)width, d_packed, d_bases, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "undelta_aggregate_device"); }
     static void transpose_delta_pack_device(std::size_t width, const T* d_in, const T* d_bases, T* d_out,
                                             std::size_t n_blocks, void* stream = nullptr)
     { detail::check(A::transpose_delta_pack((unsigned)width, d_in, d_bases, d_out, n_blocks, stream), "transpose_delta_pack_device"); }
@@ -557,6 +564,13 @@ inline void undelta_compare_range_widths_device(const std::uint8_t* d_widths, co
                                                 const T* d_bases, T lo, T hi, fl_mask_combine combine, const std::uint32_t* d_mask_in,
                                                 std::size_t n_blocks, std::uint32_t* d_mask, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::undelta_compare_range_widths(d_widths, d_offsets, d_packed, packed_bytes, d_bases, lo, hi, (int)combine, d_mask_in, n_blocks, d_mask, d_err_flag, stream), "undelta_compare_range_widths"); }
+// ... and the aggregate such a mask feeds: Delta<T>::undelta_aggregate_device over a mixed-width Delta-packed column (a block that fails
+// the device checks leaves the identity in its slot)
+template <typename T>
+inline void undelta_aggregate_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                            const T* d_bases, const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_block_aggs,
+                                            std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::undelta_aggregate_widths(d_widths, d_offsets, d_packed, packed_bytes, d_bases, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "undelta_aggregate_widths"); }
 // ... and set membership chained the same way: mask = [d_mask_in &, |] (value in the member set: a window of set_bits values from set_lo,
 // one bitmap bit each; negate: NOT IN); a block outside the window, or one the mask so far has decided, is not read
 template <typename T>
