@@ -171,6 +171,10 @@ _SIGNATURES = (
     # ({dty}: the element type of the Delta column; these rows' refusals are recorded by tests/test_delta_aggregate_cpu.py)
     ("DELTA_AGGREGATE", "fl_{dty}_undelta_aggregate", _I, [_U, _P, _P, _P, _Z, _P, _P, _P]),
     ("DELTA_AGGREGATE", "fl_{dty}_undelta_aggregate_widths", _I, [_P, _P, _P, _Z, _P, _P, _Z, _P, _P, _P]),
+    # FL_DECLARE_DELTA_SELECT (device tier): the rows a mask keeps of a DELTA-packed column, compacted in original row order
+    # (these rows' refusals are recorded by tests/test_delta_select_cpu.py)
+    ("DELTA_SELECT", "fl_{dty}_undelta_select", _I, [_U, _P, _P, _P, _P, _P, _Z, _Z, _P, _P]),
+    ("DELTA_SELECT", "fl_{dty}_undelta_select_widths", _I, [_P, _P, _P, _Z, _P, _P, _P, _P, _Z, _Z, _P, _P]),
 )
 
 # include/fastlanes_amd.h: fl_mask_combine
@@ -280,6 +284,12 @@ def delta_aggregate_symbols():
     """The symbols FL_DECLARE_DELTA_AGGREGATE declares: for all four element types the aggregate over a uniform-width and over a
     mixed-width Delta-packed column."""
     return _symbols("DELTA_AGGREGATE")
+
+
+def delta_select_symbols():
+    """The symbols FL_DECLARE_DELTA_SELECT declares: for all four element types the select over a uniform-width and over a mixed-width
+    Delta-packed column."""
+    return _symbols("DELTA_SELECT")
 
 
 _LIB = None

@@ -859,6 +859,27 @@ class Delta:
         return _aggregate_call(f"fl_{ty}_undelta_aggregate", src, n, (width, src.ptr, b.ptr), mask, block_aggs, check)
 
     @staticmethod
+    def undelta_select(width, packed, base, mask, out_offsets=None, total=None, n_blocks=None, output=None, check=True):
+        """Only the rows a selection mask keeps of a Delta-packed column: the values Delta.undelta_pack_untranspose(width, packed, base)
+        yields (ORIGINAL row order) where `mask` (the layout every compare writes and undelta_compare_range returns: a CUDA int32 tensor of
+        32 words per block, bit i = original row i) has a 1, compacted, in row order -- without writing the full-width column.  `base`
+        holds LANES = 1024/T elements per block.  A block whose mask is empty is never read; a block of width 0 (each lane's rows repeat
+        its base) reads no packed byte.  `out_offsets` / `total` / `output` / `check` are FoR.unfor_select's: mask_offsets(mask)'s results
+        (computed here if not given), with `output=None` the total is read back once to size the result (one sync), and `check=True`
+        reads the device error flag back (one sync) and raises if a block's run did not fit `output` (such a block is skipped either
+        way).  Device tier only.  n_blocks is only needed for width == 0 (default: from `base`)."""
+        src = _Arg(packed)
+        ty = src.ty
+        if not src.torch:
+            raise TypeError("undelta_select is device tier (pass CUDA tensors)")
+        lanes = 1024 // _lib.BITS[ty]
+        if n_blocks is None and width == 0:
+            n_blocks = _numel(base) // lanes
+        n = _uniform_blocks(src, width, "undelta_select", n_blocks, (mask if _is_torch(mask) else None, 32))
+        b, _ = _block_bases(src, ty, base, n)
+        return _select_call(f"fl_{ty}_undelta_select", src, n, (width, src.ptr, b.ptr), mask, out_offsets, total, output, check)
+
+    @staticmethod
     def transpose_delta_pack(width, input, base, output=None):
         """== BitPacking.pack(width, Delta.delta(Transpose.transpose(input), base)): encodes straight
         from the ORIGINAL element order.  Device tier only."""
@@ -1883,6 +1904,20 @@ def undelta_aggregate_widths(widths, offsets, packed, base, mask=None, block_agg
     n, lead = _widths_column("undelta_aggregate_widths", src, widths, offsets)
     b, aux = _block_bases(src, ty, base, n)
     return _aggregate_call(f"fl_{ty}_undelta_aggregate_widths", src, n, (*lead, *aux), mask, block_aggs, check)
+
+
+def undelta_select_widths(widths, offsets, packed, base, mask, out_offsets=None, total=None, output=None, check=True):
+    """Delta.undelta_select over a mixed-width column: the values undelta_pack_widths(widths, offsets, packed, base, untranspose=True)
+    yields where `mask` (32 words per block, bit i = original row i) has a 1, compacted, in row order; the mask of
+    undelta_compare_range_widths chains straight into it.  `out_offsets` / `total` / `output` as unfor_select_widths takes them.  The
+    per-block device checks of unfor_pack_widths, with unfor_select_widths' contract: a block that fails them, or whose run does not fit
+    `output`, is skipped (its output slots are left as they were); `check=True` reads the device error flag back (one sync) and raises,
+    `check=False` stays asynchronous."""
+    src = _Arg(packed)
+    ty = src.ty
+    n, lead = _widths_column("undelta_select_widths", src, widths, offsets)
+    b, aux = _block_bases(src, ty, base, n)
+    return _select_call(f"fl_{ty}_undelta_select_widths", src, n, (*lead, *aux), mask, out_offsets, total, output, check)
 
 
 def transpose_delta_pack_widths(widths, offsets, input, base, output, check=True):

@@ -1,9 +1,9 @@
 // fl_consumer_tier.hpp -- the host side of the consumers of a packed column (fl_for_block.hpp), and their extern "C" entry points:
 // unfor_compare, _compare_range, _compare_in, _compare_columns, _select, _aggregate, _aggregate_columns, _aggregate_by,
 // _aggregate_by_columns, _aggregate_by_window, _aggregate_by_lookup, _set_build, _lookup (and _lookup_u8) over a FoR-packed column,
-// undelta_compare_range and undelta_aggregate over a Delta-packed one.  Included by exactly one translation unit of the library (fl_capi.hip), as
+// undelta_compare_range, undelta_select and undelta_aggregate over a Delta-packed one.  Included by exactly one translation unit of the library (fl_capi.hip), as
 // fl_host_tier.hpp and fl_scan.hpp are, below that file's Column, WaveShape, with_policy, widths_args, no_bytes and FL_FOR_EACH_TYPE.
-// In this order: the column value; the refusal steps, once each; the repeated parts of the argument blocks, once each; the fifteen
+// In this order: the column value; the refusal steps, once each; the repeated parts of the argument blocks, once each; the sixteen
 // run_*, each composing the steps top to bottom in ITS order -- the status of a call with two faults depends on it, and
 // tests/test_cabi_refusals_cpu.py records it; extern "C".
 #pragma once
@@ -14,6 +14,7 @@
 #include "fl_for_compare_columns.hpp"
 #include "fl_delta_compare_range.hpp"
 #include "fl_delta_aggregate.hpp"
+#include "fl_delta_select.hpp"
 #include "fl_select.hpp"
 #include "fl_aggregate.hpp"
 #include "fl_aggregate_columns.hpp"
@@ -30,7 +31,7 @@ using namespace fl;
 
 // One packed column of a consumer: uniform-width (form.width, blocks back to back) or mixed-width (widths[] / offsets[], checked per
 // block by the kernel).  refs: FoR's references, block b's at refs[b * ref_stride] (stride 1: one per block, 0: one for the column)
-// -- or, for undelta_compare_range and undelta_aggregate, Delta's bases, with stride 0.  All columns of one call have one form.
+// -- or, for undelta_compare_range, undelta_select and undelta_aggregate, Delta's bases, with stride 0.  All columns of one call have one form.
 template <typename T> struct PackedColumn {
     Column form;
     const T* packed;
@@ -79,7 +80,7 @@ template <typename T> WaveShape block_consumer_shape()
 }
 inline WaveShape persistent_grid_shape() { return with_policy({0, 0u, 0u}); }
 // The WidthsArgs of one column; the kernels load the references with the block's metadata, so they travel beside it.  Only a
-// mixed-width column's blocks can fail a kernel's checks, so only it gets the error flag (unfor_select is the one exception).
+// mixed-width column's blocks can fail a kernel's checks, so only it gets the error flag (unfor_select and undelta_select are the exceptions).
 template <typename T> void column_args(WidthsArgs& a, const PackedColumn<T>& c, size_t n_blocks, uint32_t* err_flag, const WaveShape& sh)
 {
     widths_args<T>(a, c.form, c.packed, nullptr, nullptr, c.ref_stride, c.form.mixed ? err_flag : nullptr, n_blocks, sh);
@@ -245,6 +246,32 @@ int run_unfor_select(PackedColumn<T> col, const uint32_t* mask, const uint64_t* 
     a.out_len = out_len;
     a.sel_refs = col.refs;
     return hip_status(select_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
+}
+
+// undelta_select (fl_delta_select.hpp): unfor_select over a Delta-packed column -- col.refs are the bases (LANES per block, 128 bytes,
+// read as 16-byte cells), required and aligned.  One block per wavefront for every type, at unfor_pack_widths' occupancy.  Order
+// (unfor_select's): width; the empty column; the column, its bases, `mask`, `out_offsets` and `out`; alignment.
+template <typename T>
+int run_undelta_select(PackedColumn<T> col, const uint32_t* mask, const uint64_t* out_offsets, T* out, size_t out_len, size_t n_blocks,
+                       uint32_t* err_flag, void* stream)
+{
+    if (any_over_width(col)) return FL_ERR_WIDTH;
+    if (n_blocks == 0) return FL_OK;
+    // a selection that keeps nothing has no output: `out` may be NULL with out_len == 0, as for unfor_select
+    if (!out && out_len == 0) out = const_cast<T*>(no_bytes<T>());
+    if (!columns_present(col) || !mask || !out_offsets || !out) return FL_ERR_NULL;
+    if (any_misaligned(col.packed, col.refs, mask, out)) return FL_ERR_ALIGN;
+    const WaveShape sh = with_policy({mixed_waves(Elem<T>::BITS, false), 1u, 0u});
+    DeltaSelectArgs a;
+    column_args<T>(a, col, n_blocks, err_flag, sh);
+    a.err_flag = err_flag;                 // for a uniform-width column too: this form raises FL_DEVERR_BOUNDS (a run outside `out`)
+    a.mask = mask;
+    a.out_offsets = out_offsets;
+    a.out = reinterpret_cast<char*>(out);
+    a.out_len = out_len;
+    a.sel_refs = nullptr;
+    a.bases = reinterpret_cast<const char*>(col.refs);
+    return hip_status(delta_select_launcher<T>()(a, sh.waves, static_cast<hipStream_t>(stream)));
 }
 
 // unfor_aggregate (fl_aggregate.hpp: a block that fails the kernel's checks leaves the identity in its slot).  `mask` may be NULL:
@@ -626,6 +653,22 @@ FL_FOR_EACH_TYPE(FL_DEFINE_AGGREGATE)
         return run_undelta_aggregate<T>(mixed_column<T>(w, o, pk, pb, b, 0), mask, n, aggs, ef, s);                                  \
     }
 FL_FOR_EACH_TYPE(FL_DEFINE_DELTA_AGGREGATE)
+
+// Delta's bases stand where the reference stood, with stride 0
+#define FL_DEFINE_DELTA_SELECT(T, S)                                                                                                 \
+    int fl_##S##_undelta_select(unsigned w, const T* pk, const T* b, const uint32_t* mask, const uint64_t* oo, T* out, size_t ol,    \
+                                size_t n, uint32_t* ef, void* s)                                                                     \
+    {                                                                                                                                \
+        FL_DEVICE_TIER(s, pk, b, mask, oo, out, ef);                                                                                 \
+        return run_undelta_select<T>(uniform_column<T>(w, pk, b, 0), mask, oo, out, ol, n, ef, s);                                   \
+    }                                                                                                                                \
+    int fl_##S##_undelta_select_widths(const uint8_t* w, const uint64_t* o, const T* pk, size_t pb, const T* b, const uint32_t* mask, \
+                                       const uint64_t* oo, T* out, size_t ol, size_t n, uint32_t* ef, void* s)                       \
+    {                                                                                                                                \
+        FL_DEVICE_TIER(s, w, o, pk, b, mask, oo, out, ef);                                                                           \
+        return run_undelta_select<T>(mixed_column<T>(w, o, pk, pb, b, 0), mask, oo, out, ol, n, ef, s);                              \
+    }
+FL_FOR_EACH_TYPE(FL_DEFINE_DELTA_SELECT)
 
 #define FL_DEFINE_AGGREGATE_COLUMNS(T, S)                                                                                            \
     int fl_##S##_unfor_aggregate_columns(int ex, FL_UNIFORM_PARAMS(T, a), FL_UNIFORM_PARAMS(T, b), const uint32_t* mask, size_t n,   \

@@ -40,23 +40,6 @@ struct DeltaAggregateArgs : AggregateArgs {
     const char* bases;         // [n_blocks][128 bytes]
 };
 
-// the packed side as fl_chain.hpp's stages read it
-__device__ __forceinline__ ChainArgs chain_source_args(const DeltaAggregateArgs& a)
-{
-    ChainArgs c;
-    c.in = a.packed;
-    c.out = nullptr;
-    c.bases = a.bases;
-    c.n_blocks = a.n_blocks;
-    c.width = a.uniform_width;
-    c.widths = a.widths;
-    c.offsets = a.offsets;
-    c.err_flag = a.err_flag;
-    c.packed_bytes = a.packed_bytes;
-    c.nt_from = a.nt_from;
-    return c;
-}
-
 // The N whole mask groups of the lane's cell column (FL lanes N c + e), group e at bits e T .. e T + T - 1 of v[0..3], in EVERY lane.
 // u64: `in` is bytes 16 c .. 16 c + 15 of the block's mask, which are the two groups.  Narrower: lanes 0..7 hold the mask's 128 bytes
 // (`in` = bytes 16 lane ..), and the groups are gathered through the first 128 bytes of the wavefront's LDS image, which must be unused.

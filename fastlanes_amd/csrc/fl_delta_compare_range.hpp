@@ -32,8 +32,9 @@ struct DeltaRangeArgs : ForRangeArgs {
     const char* bases;         // [n_blocks][128 bytes]
 };
 
-// the packed side as fl_chain.hpp's stages read it
-__device__ __forceinline__ ChainArgs chain_source_args(const DeltaRangeArgs& a)
+// the packed side as fl_chain.hpp's stages read it; Args: any block-consumer argument block with Delta's `bases` beside it (this family's,
+// undelta_aggregate's, undelta_select's)
+template <typename Args> __device__ __forceinline__ ChainArgs chain_source_args(const Args& a)
 {
     ChainArgs c;
     c.in = a.packed;

@@ -21,6 +21,7 @@
 //   25 unfor_aggregate_by_lookup (count / sum / min / max per u8 attribute fetched through a key column inside a dense window of the key domain, value and key column FoR-packed and of one type: unfor_lookup_u8 and unfor_aggregate_by in one pass with no per-row output; fl_aggregate_by_lookup.hpp)
 //   26 undelta_compare_range (an interval predicate over a Delta-packed column, joined with the mask so far: the chains are decoded in place of the rows, no value is untransposed, a block its bases decide reads no packed byte; fl_delta_compare_range.hpp)
 //   27 undelta_aggregate (count / sum / min / max per block of the rows a mask keeps of a Delta-packed column: the chains are aggregated where they are decoded, each under its T-bit group of the mask, no value is untransposed, an empty-mask or width-0 block reads no packed byte; fl_delta_aggregate.hpp)
+//   28 undelta_select (the rows a mask keeps of a Delta-packed column, compacted in original row order: the chains are compacted where they are decoded, a kept row lands at the popcount of the mask below it, no value is untransposed, an empty-mask or width-0 block reads no packed byte; fl_delta_select.hpp)
 #include "fl_kernels.hpp"
 #include "fl_misc.hpp"
 #include "fl_widths.hpp"
@@ -42,6 +43,7 @@
 #include "fl_aggregate_by_lookup.hpp"
 #include "fl_delta_compare_range.hpp"
 #include "fl_delta_aggregate.hpp"
+#include "fl_delta_select.hpp"
 
 namespace fl {
 using T = FL_T;
@@ -205,7 +207,9 @@ template <> aggregate_by_lookup_launch_t aggregate_by_lookup_launcher<T>() { ret
 template <> delta_range_launch_t delta_range_launcher<T>() { return &launch_block_consumer<T, DeltaRangeArgs, k_undelta_compare_range<T>, false>; }
 #elif FL_FAMILY == 27
 template <> delta_aggregate_launch_t delta_aggregate_launcher<T>() { return &launch_block_consumer<T, DeltaAggregateArgs, k_undelta_aggregate<T>, false>; }
+#elif FL_FAMILY == 28
+template <> delta_select_launch_t delta_select_launcher<T>() { return &launch_block_consumer<T, DeltaSelectArgs, k_undelta_select<T>, false>; }
 #else
-#error "FL_FAMILY must be 0..6 or 8..27"
+#error "FL_FAMILY must be 0..6 or 8..28"
 #endif
 }  // namespace fl

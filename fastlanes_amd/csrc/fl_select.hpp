@@ -3,7 +3,7 @@
 //     out = concat over b ascending of [ unfor_pack::<W_b>(block b, references[b * ref_stride])[i]  for i ascending if bit i of block b ]
 // (ffor.rs:38-50; the mask in unpack_compare's layout: 32 words per block, bit i of block b = bit i % 32 of word b*32 + i/32, i in the
 // unpacked index order).  Block b's run starts at out + out_offsets[b] (elements): the exclusive prefix sum of the blocks' popcounts
-// (fl_scan.hpp: launch_mask_offsets), so no wavefront waits on another.  Delta columns are out of scope: a selected value needs its chain.
+// (fl_scan.hpp: launch_mask_offsets), so no wavefront waits on another.  A Delta-packed column has undelta_select (fl_delta_select.hpp).
 // The wave-per-block machinery of fl_widths.hpp, through the steps fl_for_block.hpp shares among the four consumers of a packed column:
 //   * a block's width, offset, reference, out_offsets[b] AND its 128-byte mask arrive together (independent vector loads, one wait);
 //     its preconditions are checked (block_precondition: a failing block is skipped, its output slots untouched), and a block whose

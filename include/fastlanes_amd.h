@@ -444,8 +444,8 @@ FL_DECLARE_FOR_COMPARE_RANGE(uint64_t, u64)
  * block b = bit i % 32 of word b*32 + i/32, i in the unpacked index order):
  *     out = concat over b ascending of [ unfor_pack::<W_b>(block b, references[b*reference_stride])[i]  for i ascending if bit i ]
  * (ffor.rs:38-50) -- the kept values, compacted, in column order.  A plain bit-packed column is selected with one zero reference and
- * reference_stride 0.  Delta columns are out of scope: a selected value needs its whole chain.  Two steps, both asynchronous on
- * `stream`, no allocation, no synchronisation:
+ * reference_stride 0.  A Delta-packed column has fl_<ty>_undelta_select (below).  Two steps, both asynchronous on `stream`, no
+ * allocation, no synchronisation:
  *   1. the mask-offsets call (type-independent): out_offsets[b] = number of mask bits set in blocks 0..b-1 (a device uint64 array, in
  *      ELEMENTS), *total (device uint64, may be NULL) = the number of kept values.  Three small launches, no scratch memory.
  *   2. fl_<ty>_unfor_select / fl_<ty>_unfor_select_widths: block b's kept values go to out[out_offsets[b] ..].  The count is taken from
@@ -1047,8 +1047,8 @@ FL_DECLARE_AGGREGATE_BY_LOOKUP(uint64_t, u64)
  * width > T is FL_ERR_WIDTH (also for an empty column); a `combine` outside the enum FL_ERR_INDEX; n_blocks == 0 FL_OK; mask_in ==
  * NULL with AND / OR, or any other required pointer NULL, FL_ERR_NULL (`in` / `packed` may be NULL only when no byte can be read:
  * width 0, or packed_bytes == 0); the packed column, `bases`, `mask` and `mask_in` are 16-byte aligned (FL_ERR_ALIGN).
- * Out of scope: masks in transposed order; the Delta form of select and the grouped Delta aggregates (fl_<ty>_undelta_aggregate, below,
- * aggregates one Delta column under such a mask); the host tier.
+ * Out of scope: masks in transposed order; the grouped Delta aggregates (fl_<ty>_undelta_aggregate and fl_<ty>_undelta_select, below,
+ * aggregate and materialise one Delta column under such a mask); the host tier.
  * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
  * are pinned surfaces.)
  */
@@ -1087,8 +1087,8 @@ FL_DECLARE_DELTA_COMPARE_RANGE(uint64_t, u64)
  * width > T is FL_ERR_WIDTH (also for an empty column); n_blocks == 0 FL_OK; a required pointer NULL FL_ERR_NULL (`bases` is required;
  * `in` / `packed` may be NULL only when no byte can be read: width 0, or packed_bytes == 0); the packed column, `bases`, `mask` and
  * `block_aggs` are 16-byte aligned (FL_ERR_ALIGN).
- * Out of scope: the Delta form of select (it needs original-order compaction), grouped or two-column Delta aggregates, masks in
- * transposed order, signed columns, the host tier.
+ * Out of scope: grouped or two-column Delta aggregates, masks in transposed order, signed columns, the host tier (the Delta form of
+ * select is fl_<ty>_undelta_select, below).
  * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
  * are pinned surfaces.)
  */
@@ -1105,6 +1105,43 @@ FL_DECLARE_DELTA_AGGREGATE(uint8_t, u8)
 FL_DECLARE_DELTA_AGGREGATE(uint16_t, u16)
 FL_DECLARE_DELTA_AGGREGATE(uint32_t, u32)
 FL_DECLARE_DELTA_AGGREGATE(uint64_t, u64)
+
+/*
+ * EXTENSION (SURVEY.md 8(f2) "unpack -> filter", 8(f4) "take"): DECODE ONLY THE ROWS A SELECTION MASK KEEPS OF A DELTA-PACKED COLUMN,
+ * uniform or mixed width -- SELECT l_shipdate WHERE <chain of predicates> on the sorted or nearly sorted columns a FastLanes writer
+ * stores Delta-coded -- with no full-width decoded column written or read back.  Defined as the composition (arithmetic mod 2^T)
+ *     v[b] = untranspose(undelta_pack::<W_b>(block b, bases[b*LANES .. b*LANES + LANES]))         (delta.rs:47-63, transpose.rs:17-22)
+ *     out  = concat over b ascending of [ v[b][i]  for i ascending if bit i of block b of mask ]
+ * -- the kept values, compacted, in ORIGINAL row order.  The mask is the one every compare entry point writes and
+ * fl_<ty>_undelta_compare_range produces: 32 words per block, bit i = the ORIGINAL row i, LSB first.  `bases` holds LANES = 1024 / T
+ * elements per block (128 bytes), as for fl_<ty>_undelta_pack.  The two steps are fl_<ty>_unfor_select's: fl_mask_offsets gives
+ * out_offsets / *total (per-block popcounts do not depend on the row order), then block b's kept values go to out[out_offsets[b] ..].
+ * Everything else is fl_<ty>_unfor_select's contract too: the count is taken from the block's own mask bits; a block whose run does not
+ * lie inside [0, out_len) is SKIPPED and FL_DEVERR_BOUNDS is ORed into *err_flag (`err_flag` serves the uniform form too); the
+ * mixed-width form runs the per-block device checks of fl_<ty>_unfor_pack_widths, and a failing block is skipped, its output slots left
+ * untouched, its FL_DEVERR_* bit raised.  A block whose mask is all zero reads nothing and stores nothing; a block of width 0 (each
+ * lane's T rows repeat its base) reads no packed byte.  Device tier, asynchronous on `stream`; allocates nothing, uses no scratch memory.
+ * width > T is FL_ERR_WIDTH (also for an empty column); n_blocks == 0 FL_OK; a required pointer NULL FL_ERR_NULL (`bases`, `mask` and
+ * `out_offsets` are required; `in` / `packed` may be NULL only when no byte can be read: width 0, or packed_bytes == 0; `out` may be
+ * NULL when out_len is 0: a selection that keeps nothing has no output); the packed column, `bases`, `mask` and `out` are 16-byte
+ * aligned (FL_ERR_ALIGN); a block's own destination is only element-aligned.
+ * Out of scope: masks in transposed order, signed columns (the bit patterns are the same), the host tier.
+ * (Declared by a macro of its own: FL_DECLARE_TYPE's per-type list, the list of other functions and the other macros' symbol lists
+ * are pinned surfaces.)
+ */
+#define FL_DECLARE_DELTA_SELECT(T, S)                                                                     \
+    int fl_##S##_undelta_select(unsigned width, const T *in, const T *bases,                              \
+                                const uint32_t *mask, const uint64_t *out_offsets, T *out, size_t out_len, \
+                                size_t n_blocks, uint32_t *err_flag, void *stream);                       \
+    int fl_##S##_undelta_select_widths(const uint8_t *widths, const uint64_t *offsets, const T *packed,   \
+                                       size_t packed_bytes, const T *bases, const uint32_t *mask,         \
+                                       const uint64_t *out_offsets, T *out, size_t out_len,               \
+                                       size_t n_blocks, uint32_t *err_flag, void *stream);
+
+FL_DECLARE_DELTA_SELECT(uint8_t, u8)
+FL_DECLARE_DELTA_SELECT(uint16_t, u16)
+FL_DECLARE_DELTA_SELECT(uint32_t, u32)
+FL_DECLARE_DELTA_SELECT(uint64_t, u64)
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,8 @@ template <typename T> struct Abi;
         static constexpr auto undelta_compare_range_widths = fl_##S##_undelta_compare_range_widths;  \
         static constexpr auto undelta_aggregate = fl_##S##_undelta_aggregate;                        \
         static constexpr auto undelta_aggregate_widths = fl_##S##_undelta_aggregate_widths;          \
+        static constexpr auto undelta_select = fl_##S##_undelta_select;                              \
+        static constexpr auto undelta_select_widths = fl_##S##_undelta_select_widths;                \
         static constexpr auto unfor_compare_columns = fl_##S##_unfor_compare_columns;                \
         static constexpr auto unfor_compare_columns_widths = fl_##S##_unfor_compare_columns_widths;  \
         static constexpr auto unfor_select = fl_##S##_unfor_select;                                  \
@@ -354,6 +356,12 @@ template <typename T> struct Delta : BitPacking<T> {
     static void undelta_aggregate_device(std::size_t width, const T* d_packed, const T* d_bases, const std::uint32_t* d_mask, std::size_t n_blocks,
                                          fl_block_aggregate* d_block_aggs, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
     { detail::check(A::undelta_aggregate((unsigned)width, d_packed, d_bases, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "undelta_aggregate_device"); }
+    // the rows d_mask keeps of the Delta-packed column, compacted in original row order: block b's run at d_out + d_out_offsets[b]
+    // (mask_offsets_device's results), as FoR<T>::unfor_select_device writes it; no full-width decoded column is written
+    static void undelta_select_device(std::size_t width, const T* d_packed, const T* d_bases, const std::uint32_t* d_mask,
+                                      const std::uint64_t* d_out_offsets, T* d_out, std::size_t out_len, std::size_t n_blocks,
+                                      std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+    { detail::check(A::undelta_select((unsigned)width, d_packed, d_bases, d_mask, d_out_offsets, d_out, out_len, n_blocks, d_err_flag, stream), "undelta_select_device"); }
     static void transpose_delta_pack_device(std::size_t width, const T* d_in, const T* d_bases, T* d_out,
                                             std::size_t n_blocks, void* stream = nullptr)
     { detail::check(A::transpose_delta_pack((unsigned)width, d_in, d_bases, d_out, n_blocks, stream), "transpose_delta_pack_device"); }
@@ -571,6 +579,13 @@ inline void undelta_aggregate_widths_device(const std::uint8_t* d_widths, const 
                                             const T* d_bases, const std::uint32_t* d_mask, std::size_t n_blocks, fl_block_aggregate* d_block_aggs,
                                             std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
 { detail::check(detail::Abi<T>::undelta_aggregate_widths(d_widths, d_offsets, d_packed, packed_bytes, d_bases, d_mask, n_blocks, d_block_aggs, d_err_flag, stream), "undelta_aggregate_widths"); }
+// ... and the rows such a mask keeps, materialised: Delta<T>::undelta_select_device over a mixed-width Delta-packed column (a block that
+// fails the device checks, or whose run does not fit d_out, is skipped and its output slots are left untouched)
+template <typename T>
+inline void undelta_select_widths_device(const std::uint8_t* d_widths, const std::uint64_t* d_offsets, const T* d_packed, std::size_t packed_bytes,
+                                         const T* d_bases, const std::uint32_t* d_mask, const std::uint64_t* d_out_offsets, T* d_out,
+                                         std::size_t out_len, std::size_t n_blocks, std::uint32_t* d_err_flag = nullptr, void* stream = nullptr)
+{ detail::check(detail::Abi<T>::undelta_select_widths(d_widths, d_offsets, d_packed, packed_bytes, d_bases, d_mask, d_out_offsets, d_out, out_len, n_blocks, d_err_flag, stream), "undelta_select_widths"); }
 // ... and set membership chained the same way: mask = [d_mask_in &, |] (value in the member set: a window of set_bits values from set_lo,
 // one bitmap bit each; negate: NOT IN); a block outside the window, or one the mask so far has decided, is not read
 template <typename T>
