@@ -1213,8 +1213,10 @@ def test_streams_and_graph_capture(fl, oracle):
 
 
 def test_mixed_plan_column_beyond_4GiB(fl, oracle):
-    """A 4.9 GB unpacked column (600 001 u64 blocks; two width-2 blocks at its ends among width-1 blocks):
-    64-bit block addressing -- nothing in the mixed path may assume a 32-bit window."""
+    """A 4.9 GB UNPACKED column (600 001 u64 blocks; two width-2 blocks at its ends among width-1 blocks): the unpacked side's
+    byte addresses pass 4 GiB, in MixedWidthPlan's unpack and pack.  The packed column is 77 MB, so every packed offset fits 32 bits
+    with room to spare: offsets[b] at and above 2^31 / 2^32 is tests/test_gpu_far_columns.py's subject, and only `unpack` and `pack`
+    of a plan run here -- no consumer does."""
     import torch
     n = 600_001
     widths = np.ones(n, dtype=np.uint8)
