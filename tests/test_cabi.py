@@ -247,9 +247,20 @@ def test_cpp_trait_mirror_builds_and_fails_loudly_without_gpu(lib):
         assert r.returncode == 2 and "HIP runtime error" in r.stdout, (r.returncode, r.stdout)
 
 
-def build_cpp_test():
+def test_cpp_query_mirror_builds_and_fails_loudly_without_gpu(lib):
+    """tests/cpp/test_query_mirror.cpp (one query of each storage form through the mirror, tests/test_gpu_cpp_mirror.py) compiles and links
+    against the C ABI; with no GPU it says so and exits 2 instead of passing"""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "cpp", "test_trait_mirror")
+    import torch
+    exe = build_cpp_test("test_query_mirror")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    if not torch.cuda.is_available():
+        assert r.returncode == 2 and "HIP runtime error" in r.stdout, (r.returncode, r.stdout)
+
+
+def build_cpp_test(name="test_trait_mirror"):
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "cpp", name)
     src = exe + ".cpp"
     hdr = os.path.join(ROOT, "include", "fastlanes_amd.hpp")
     if not os.path.exists(exe) or max(os.path.getmtime(src), os.path.getmtime(hdr)) > os.path.getmtime(exe):
